@@ -8,6 +8,7 @@ can't first appear on the 8-GPU box."""
 
 import io
 import json
+import os
 import sys
 
 from dist_util import run_distributed
@@ -47,6 +48,58 @@ def _check(out, world, parallelism):
         assert k in rank0, k
     # only rank 0 prints
     assert all(o is None for o in out[1:])
+
+
+def test_bench_n1_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's results as float32
+    .npy; that step starts from the seeded weights, so two runs with
+    the same arguments write identical files. --steps sets
+    the number of timed steps and ms_per_step is per timed step."""
+    import numpy as np
+
+    outs = []
+    for name in ("a", "b"):
+        d = str(tmp_path / name)
+        extra = ("--steps", "2", "--warmup", "1", "--full",
+                 "--dump-outputs", d)
+        res = run_distributed(_bench_body, 1, (extra,), timeout=300)
+        _check(res, 1, "single")
+        assert res[0]["steps"] == 2 and res[0]["warmup"] == 1
+        # 8 images per step: value [img/s] and ms_per_step agree
+        assert abs(res[0]["value"] * res[0]["ms_per_step"] / 8e3 - 1) < 1e-6
+        outs.append({f: np.load(tmp_path / name / f)
+                     for f in sorted(os.listdir(d))})
+    a, b = outs
+    assert sorted(a) == ["logits.npy", "loss.npy", "params_sample.npy"]
+    assert a["logits.npy"].shape == (8, 10) and a["loss.npy"].shape == (4,)
+    for f in a:
+        assert a[f].dtype == np.float32 and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+    # the dumped step restarts from the seeded weights: a run whose only
+    # step is the first one computes the same arrays
+    d = str(tmp_path / "c")
+    run_distributed(_bench_body, 1, (("--dump-outputs", d),), timeout=300)
+    for f in a:
+        assert np.array_equal(a[f], np.load(tmp_path / "c" / f)), f
+    # the parameter sample carries the step's backward pass and update:
+    # another learning rate leaves the forward outputs alone and moves
+    # the sampled parameters by exactly the ratio of the two rates
+    d = str(tmp_path / "d")
+    run_distributed(_bench_body, 1, (("--dump-outputs", d, "--lr", "0"),),
+                    timeout=300)
+    d = str(tmp_path / "e")
+    run_distributed(_bench_body, 1, (("--dump-outputs", d, "--lr", "0.02"),),
+                    timeout=300)
+    p0, p2 = (np.load(tmp_path / n / "params_sample.npy") for n in "de")
+    for n in "de":
+        for f in ("logits.npy", "loss.npy"):
+            assert np.array_equal(a[f], np.load(tmp_path / n / f)), (n, f)
+    p1 = a["params_sample.npy"]
+    moved = np.abs(p1 - p0)
+    assert (moved > 0).mean() > 0.5  # the gradient reaches the sample
+    assert np.allclose(p2 - p0, 2 * (p1 - p0), rtol=1e-4,
+                       atol=1e-6 * float(np.abs(p0).max()))
 
 
 def test_bench_n2_pp():
