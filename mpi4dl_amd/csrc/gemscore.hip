@@ -251,11 +251,8 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
         // compile-time (k,s): span stays in registers, loops fully unroll
         constexpr int SPAN = KK > 0 ? 8 * SS + KK - SS : 1;
         float seg[SPAN];
-        // NOTE: a vectorized span-load variant (bf16 reinterpret, then a
-        // type-generic memcpy form) was measured and REVERTED: the
-        // reinterpret broke fp32 instantiations, and the memcpy form
-        // regressed the bench ~5% (the local span array drops to
-        // scratch). Scalar loads + L1 hitting the overlapped spans stay.
+        // 2-byte dtypes take the *_vec kernels below: explicit 16-byte vector
+        // types there, because a type-generic memcpy span drops to scratch.
 #pragma unroll
         for (int j = 0; j < SPAN; ++j) {
           const int w = w_lo + j;
@@ -303,7 +300,7 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ go,
                                    const uint8_t* __restrict__ idx,
                                    T* __restrict__ gi, int64_t NC, int H,
                                    int W, int OH, int OW, int k_, int s_,
-                                   int p) {
+                                   int p, int64_t C, int64_t go_bs) {
   const int k = KK > 0 ? KK : k_;
   const int s = KK > 0 ? SS : s_;
   const int W8 = (W + 7) / 8;
@@ -322,7 +319,8 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ go,
     int oh_hi = (h + p) / s; if (oh_hi > OH - 1) oh_hi = OH - 1;
     int ow_lo = (w0 + p - k + 1 + s - 1) / s; if (ow_lo < 0) ow_lo = 0;
     int ow_hi = (w0 + 7 + p) / s; if (ow_hi > OW - 1) ow_hi = OW - 1;
-    const T* gop = go + plane * OH * OW;
+    // go may be a channel slice of a wider NCHW tensor (batch stride go_bs)
+    const T* gop = go + (plane / C) * go_bs + (plane % C) * OH * OW;
     const uint8_t* ip = idx + plane * OH * OW;
     // at most ceil((8 + k - 1)/s) + 1 candidate columns
     constexpr int NOW = KK > 0 ? (8 + KK - 1) / SS + 1 : 0;
@@ -444,7 +442,8 @@ template <typename T, int KK, int SS>
 __global__ void avgpool_bwd_kernel(const T* __restrict__ go, T* __restrict__ gi,
                                    int64_t NC, int H, int W, int OH, int OW,
                                    int k_, int s_, int p, long gr0, long gc0,
-                                   long Hg, long Wg, int include_pad) {
+                                   long Hg, long Wg, int include_pad,
+                                   int64_t C, int64_t go_bs) {
   const int k = KK > 0 ? KK : k_;
   const int s = KK > 0 ? SS : s_;
   const int W8 = (W + 7) / 8;
@@ -463,7 +462,7 @@ __global__ void avgpool_bwd_kernel(const T* __restrict__ go, T* __restrict__ gi,
     int oh_hi = (h + p) / s; if (oh_hi > OH - 1) oh_hi = OH - 1;
     int ow_lo = (w0 + p - k + 1 + s - 1) / s; if (ow_lo < 0) ow_lo = 0;
     int ow_hi = (w0 + 7 + p) / s; if (ow_hi > OW - 1) ow_hi = OW - 1;
-    const T* gop = go + plane * OH * OW;
+    const T* gop = go + (plane / C) * go_bs + (plane % C) * OH * OW;
     // interior iff every touched window lies fully inside the global image
     const bool interior =
         include_pad ||
@@ -525,6 +524,572 @@ __global__ void avgpool_bwd_kernel(const T* __restrict__ go, T* __restrict__ gi,
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       if (w0 + e < W) gi[ibase + w0 + e] = (T)acc[e];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Vectorised pooling for 2-byte dtypes (bf16 / fp16).
+//
+// Host-side predicate (pool_vec_ok): W % 8 == 0, OW % 8 == 0, 16-byte
+// aligned bases, geometry (k,s,p) in {(3,1,1), (3,2,1), (2,2,0)}. Each
+// thread owns one 16-byte column chunk and walks a strip of POOL_R rows
+// with a sliding register window, so every row is loaded once per thread
+// with one 16-byte load (+ one narrow neighbour load per side, an L1 hit).
+// Only the first/last chunk of a row and out-of-plane rows are predicated.
+//
+// Results are bit-identical to the generic kernels above: the same scan
+// order and strict '>' for max (so the same u8 index), the same fp32
+// summation order and divisions for avg. Adding +0.f for a padded tap
+// equals skipping it because no accumulator here can hold -0.f.
+// ---------------------------------------------------------------------------
+
+constexpr int POOL_R = 4;  // rows per strip
+
+template <typename T>
+__device__ __forceinline__ void ld8f(const T* __restrict__ p, float* f) {
+  const s16x8_ v = *(const s16x8_*)p;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = (float)((const T*)&v)[e];
+}
+
+template <typename T>
+__device__ __forceinline__ void st8f(T* __restrict__ p, const float* f) {
+  s16x8_ v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ((T*)&v)[e] = (T)f[e];
+  *(s16x8_*)p = v;
+}
+
+__device__ __forceinline__ void ld8idx(const uint8_t* __restrict__ p, int* o) {
+  const uint2 v = *(const uint2*)p;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    o[e] = (int)((v.x >> (8 * e)) & 255u);
+    o[4 + e] = (int)((v.y >> (8 * e)) & 255u);
+  }
+}
+
+__device__ __forceinline__ void st8idx(uint8_t* __restrict__ p, const int* o) {
+  uint2 v;
+  v.x = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) |
+        ((uint32_t)o[3] << 24);
+  v.y = (uint32_t)o[4] | ((uint32_t)o[5] << 8) | ((uint32_t)o[6] << 16) |
+        ((uint32_t)o[7] << 24);
+  *(uint2*)p = v;
+}
+
+// Row maxima of a 3-wide window for 8 outputs: m[e] / kw[e] are the first
+// maximum of input row h over columns (8c+e)*S-1 .. +2 (strict '>' from
+// -inf, kw 0 when nothing beats -inf). xc points at column 8*S*c of the
+// plane. Out-of-plane rows give (-inf, 0), which never wins downstream.
+template <typename T, int S>
+__device__ __forceinline__ void max3_row(const T* __restrict__ xc, int h, int H,
+                                         int W, bool hasl, bool hasr, float* m,
+                                         int* kw) {
+  constexpr int SPAN = 8 * S + 3 - S;  // 10 (s=1) or 17 (s=2)
+  float seg[SPAN];
+  if (h < 0 || h >= H) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { m[e] = -INFINITY; kw[e] = 0; }
+    return;
+  }
+  const T* row = xc + (int64_t)h * W;
+  seg[0] = hasl ? (float)row[-1] : -INFINITY;
+  ld8f(row, seg + 1);
+  if (S == 2) ld8f(row + 8, seg + 9);
+  else seg[9] = hasr ? (float)row[8] : -INFINITY;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float b = -INFINITY;
+    int bi = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float v = seg[e * S + j];
+      if (v > b) { b = v; bi = j; }
+    }
+    m[e] = b;
+    kw[e] = bi;
+  }
+}
+
+// max pool k3 p1, stride S in {1,2}. Scanning the three row maxima in kh
+// order with strict '>' picks the first maximum in kh-major, kw-minor
+// order, exactly like the generic scan.
+template <typename T, int S>
+__global__ void __launch_bounds__(256)
+maxpool3_fwd_vec(const T* __restrict__ x, T* __restrict__ y,
+                 uint8_t* __restrict__ idx, int64_t NC, int H, int W, int OH,
+                 int OW) {
+  const int CH = OW >> 3;
+  const int NS = (OH + POOL_R - 1) / POOL_R;
+  const int64_t total = NC * NS * CH;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += stride) {
+    const int c = (int)(t % CH);
+    const int64_t q = t / CH;
+    const int oh0 = (int)(q % NS) * POOL_R;
+    const int64_t plane = q / NS;
+    const T* xc = x + plane * H * W + c * 8 * S;
+    const int64_t ob = plane * OH * OW + c * 8;
+    const bool hasl = c > 0, hasr = c < CH - 1;
+    float ma[8], mb[8], mc[8];
+    int ka[8], kb[8], kc[8];
+    max3_row<T, S>(xc, oh0 * S - 1, H, W, hasl, hasr, ma, ka);
+    if (S == 1) max3_row<T, S>(xc, oh0, H, W, hasl, hasr, mb, kb);
+#pragma unroll
+    for (int r = 0; r < POOL_R; ++r) {
+      const int oh = oh0 + r;
+      if (oh >= OH) break;
+      if (S == 2) max3_row<T, S>(xc, oh * 2, H, W, hasl, hasr, mb, kb);
+      max3_row<T, S>(xc, oh * S + 1, H, W, hasl, hasr, mc, kc);
+      float best[8];
+      int bi[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float b = -INFINITY;
+        int i = 0;
+        if (ma[e] > b) { b = ma[e]; i = ka[e]; }
+        if (mb[e] > b) { b = mb[e]; i = 3 + kb[e]; }
+        if (mc[e] > b) { b = mc[e]; i = 6 + kc[e]; }
+        best[e] = b;
+        bi[e] = i;
+      }
+      st8f(y + ob + (int64_t)oh * OW, best);
+      st8idx(idx + ob + (int64_t)oh * OW, bi);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (S == 1) { ma[e] = mb[e]; ka[e] = kb[e]; mb[e] = mc[e]; kb[e] = kc[e]; }
+        else { ma[e] = mc[e]; ka[e] = kc[e]; }
+      }
+    }
+  }
+}
+
+// max pool k2 s2 p0: 16 input columns -> 8 outputs, no padding anywhere.
+template <typename T>
+__global__ void __launch_bounds__(256)
+maxpool2s2_fwd_vec(const T* __restrict__ x, T* __restrict__ y,
+                   uint8_t* __restrict__ idx, int64_t NC, int H, int W, int OH,
+                   int OW) {
+  const int CH = OW >> 3;
+  const int NS = (OH + POOL_R - 1) / POOL_R;
+  const int64_t total = NC * NS * CH;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += stride) {
+    const int c = (int)(t % CH);
+    const int64_t q = t / CH;
+    const int oh0 = (int)(q % NS) * POOL_R;
+    const int64_t plane = q / NS;
+    const T* xc = x + plane * H * W + c * 16;
+    const int64_t ob = plane * OH * OW + c * 8;
+#pragma unroll
+    for (int r = 0; r < POOL_R; ++r) {
+      const int oh = oh0 + r;
+      if (oh >= OH) break;
+      float s0[16], s1[16];
+      const T* row = xc + (int64_t)(oh * 2) * W;
+      ld8f(row, s0);
+      ld8f(row + 8, s0 + 8);
+      ld8f(row + W, s1);
+      ld8f(row + W + 8, s1 + 8);
+      float best[8];
+      int bi[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float b = -INFINITY;
+        int i = 0;
+        if (s0[2 * e] > b) { b = s0[2 * e]; i = 0; }
+        if (s0[2 * e + 1] > b) { b = s0[2 * e + 1]; i = 1; }
+        if (s1[2 * e] > b) { b = s1[2 * e]; i = 2; }
+        if (s1[2 * e + 1] > b) { b = s1[2 * e + 1]; i = 3; }
+        best[e] = b;
+        bi[e] = i;
+      }
+      st8f(y + ob + (int64_t)oh * OW, best);
+      st8idx(idx + ob + (int64_t)oh * OW, bi);
+    }
+  }
+}
+
+// One row of (go, idx) candidates for a backward thread: NJ = 10 covers
+// ow = 8c-1 .. 8c+8 (stride 1), NJ = 9 covers ow = 8c .. 8c+8 (k3 s2).
+// Invalid candidates get g = 0 and the impossible window offset 255.
+template <typename T, int NJ>
+__device__ __forceinline__ void go_row(const T* __restrict__ gc,
+                                       const uint8_t* __restrict__ ic, int oh,
+                                       int OH, int OW, bool hasl, bool hasr,
+                                       float* g, int* o) {
+  constexpr int L = NJ - 9;  // 1 when a left neighbour is needed
+  if (oh < 0 || oh >= OH) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { g[j] = 0.f; o[j] = 255; }
+    return;
+  }
+  const T* gr = gc + (int64_t)oh * OW;
+  const uint8_t* ir = ic + (int64_t)oh * OW;
+  ld8f(gr, g + L);
+  ld8idx(ir, o + L);
+  if (L == 1) {
+    g[0] = hasl ? (float)gr[-1] : 0.f;
+    o[0] = hasl ? (int)ir[-1] : 255;
+  }
+  g[L + 8] = hasr ? (float)gr[8] : 0.f;
+  o[L + 8] = hasr ? (int)ir[8] : 255;
+}
+
+// max pool backward k3 s1 p1. Input (h, 8c+e) gathers from go rows
+// h-1, h, h+1 (kh = 2, 1, 0) and columns ow = 8c+e-1 .. +1 (kw = 2, 1, 0),
+// added in ascending (oh, ow) order like the generic kernel.
+template <typename T>
+__global__ void __launch_bounds__(256)
+maxpool3s1_bwd_vec(const T* __restrict__ go, const uint8_t* __restrict__ idx,
+                   T* __restrict__ gi, int64_t NC, int H, int W, int64_t C,
+                   int64_t go_bs) {
+  const int CH = W >> 3;
+  const int NS = (H + POOL_R - 1) / POOL_R;
+  const int64_t total = NC * NS * CH;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += stride) {
+    const int c = (int)(t % CH);
+    const int64_t q = t / CH;
+    const int h0 = (int)(q % NS) * POOL_R;
+    const int64_t plane = q / NS;
+    const int64_t HW = (int64_t)H * W;
+    const T* gc = go + (plane / C) * go_bs + (plane % C) * HW + c * 8;
+    const uint8_t* ic = idx + plane * HW + c * 8;
+    T* gic = gi + plane * HW + c * 8;
+    const bool hasl = c > 0, hasr = c < CH - 1;
+    float g0[10], g1[10], g2[10];
+    int o0[10], o1[10], o2[10];
+    go_row<T, 10>(gc, ic, h0 - 1, H, W, hasl, hasr, g0, o0);
+    go_row<T, 10>(gc, ic, h0, H, W, hasl, hasr, g1, o1);
+#pragma unroll
+    for (int r = 0; r < POOL_R; ++r) {
+      const int h = h0 + r;
+      if (h >= H) break;
+      go_row<T, 10>(gc, ic, h + 1, H, W, hasl, hasr, g2, o2);
+      float acc[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a += (o0[e + j] == 6 + 2 - j) ? g0[e + j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a += (o1[e + j] == 3 + 2 - j) ? g1[e + j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a += (o2[e + j] == 2 - j) ? g2[e + j] : 0.f;
+        acc[e] = a;
+      }
+      st8f(gic + (int64_t)h * W, acc);
+#pragma unroll
+      for (int j = 0; j < 10; ++j) {
+        g0[j] = g1[j]; o0[j] = o1[j];
+        g1[j] = g2[j]; o1[j] = o2[j];
+      }
+    }
+  }
+}
+
+// max pool backward k3 s2 p1: 16 input columns <- 9 candidate outputs per
+// go row. Input rows come in pairs: row 2q gathers from go row q (kh = 1),
+// row 2q+1 from go row q (kh = 2) then q+1 (kh = 0). Even columns 2m see
+// (ow = 8c+m, kw = 1); odd columns 2m+1 see (m, kw = 2) then (m+1, kw = 0).
+template <typename T>
+__global__ void __launch_bounds__(256)
+maxpool3s2_bwd_vec(const T* __restrict__ go, const uint8_t* __restrict__ idx,
+                   T* __restrict__ gi, int64_t NC, int H, int W, int OH, int OW,
+                   int64_t C, int64_t go_bs) {
+  const int CH = OW >> 3;  // == W / 16
+  const int NP = (H + 1) >> 1;  // input row pairs (== OH)
+  const int NS = (NP + POOL_R - 1) / POOL_R;
+  const int64_t total = NC * NS * CH;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += stride) {
+    const int c = (int)(t % CH);
+    const int64_t q = t / CH;
+    const int p0 = (int)(q % NS) * POOL_R;
+    const int64_t plane = q / NS;
+    const int64_t OHW = (int64_t)OH * OW;
+    const T* gc = go + (plane / C) * go_bs + (plane % C) * OHW + c * 8;
+    const uint8_t* ic = idx + plane * OHW + c * 8;
+    T* gic = gi + plane * (int64_t)H * W + c * 16;
+    const bool hasr = c < CH - 1;
+    float ga[9], gb[9];
+    int oa[9], ob[9];
+    go_row<T, 9>(gc, ic, p0, OH, OW, false, hasr, ga, oa);
+#pragma unroll
+    for (int r = 0; r < POOL_R; ++r) {
+      const int pr = p0 + r;
+      if (pr >= NP) break;
+      go_row<T, 9>(gc, ic, pr + 1, OH, OW, false, hasr, gb, ob);
+      float acc[16];
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        float a = 0.f;
+        a += (oa[m] == 4) ? ga[m] : 0.f;
+        acc[2 * m] = a;
+        float b = 0.f;
+        b += (oa[m] == 5) ? ga[m] : 0.f;
+        b += (oa[m + 1] == 3) ? ga[m + 1] : 0.f;
+        acc[2 * m + 1] = b;
+      }
+      T* row = gic + (int64_t)(2 * pr) * W;
+      st8f(row, acc);
+      st8f(row + 8, acc + 8);
+      if (2 * pr + 1 < H) {
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+          float a = 0.f;
+          a += (oa[m] == 7) ? ga[m] : 0.f;
+          a += (ob[m] == 1) ? gb[m] : 0.f;
+          acc[2 * m] = a;
+          float b = 0.f;
+          b += (oa[m] == 8) ? ga[m] : 0.f;
+          b += (oa[m + 1] == 6) ? ga[m + 1] : 0.f;
+          b += (ob[m] == 2) ? gb[m] : 0.f;
+          b += (ob[m + 1] == 0) ? gb[m + 1] : 0.f;
+          acc[2 * m + 1] = b;
+        }
+        st8f(row + W, acc);
+        st8f(row + W + 8, acc + 8);
+      }
+#pragma unroll
+      for (int j = 0; j < 9; ++j) { ga[j] = gb[j]; oa[j] = ob[j]; }
+    }
+  }
+}
+
+// max pool backward k2 s2 p0: input (h, w) has the single candidate
+// (h/2, w/2), window offset (h%2)*2 + w%2. An odd last row has none.
+template <typename T>
+__global__ void __launch_bounds__(256)
+maxpool2s2_bwd_vec(const T* __restrict__ go, const uint8_t* __restrict__ idx,
+                   T* __restrict__ gi, int64_t NC, int H, int W, int OH, int OW,
+                   int64_t C, int64_t go_bs) {
+  const int CH = OW >> 3;  // == W / 16
+  const int NP = (H + 1) >> 1;
+  const int NS = (NP + POOL_R - 1) / POOL_R;
+  const int64_t total = NC * NS * CH;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += stride) {
+    const int c = (int)(t % CH);
+    const int64_t q = t / CH;
+    const int p0 = (int)(q % NS) * POOL_R;
+    const int64_t plane = q / NS;
+    const int64_t OHW = (int64_t)OH * OW;
+    const T* gc = go + (plane / C) * go_bs + (plane % C) * OHW + c * 8;
+    const uint8_t* ic = idx + plane * OHW + c * 8;
+    T* gic = gi + plane * (int64_t)H * W + c * 16;
+#pragma unroll
+    for (int r = 0; r < POOL_R; ++r) {
+      const int pr = p0 + r;
+      if (pr >= NP) break;
+      float g[8];
+      int o[8];
+      if (pr < OH) {
+        ld8f(gc + (int64_t)pr * OW, g);
+        ld8idx(ic + (int64_t)pr * OW, o);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { g[e] = 0.f; o[e] = 255; }
+      }
+      T* row = gic + (int64_t)(2 * pr) * W;
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh) {
+        if (2 * pr + kh >= H) break;
+        float acc[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          float a = 0.f;
+          a += (o[e >> 1] == kh * 2 + (e & 1)) ? g[e >> 1] : 0.f;
+          acc[e] = a;
+        }
+        st8f(row + (int64_t)kh * W, acc);
+        st8f(row + (int64_t)kh * W + 8, acc + 8);
+      }
+    }
+  }
+}
+
+// One input row of avg pool k3 s1 p1 taps: columns 8c-1 .. 8c+8, zeros
+// for padding.
+template <typename T>
+__device__ __forceinline__ void avg_row(const T* __restrict__ xc, int h, int H,
+                                        int W, bool hasl, bool hasr,
+                                        float* seg) {
+  if (h < 0 || h >= H) {
+#pragma unroll
+    for (int j = 0; j < 10; ++j) seg[j] = 0.f;
+    return;
+  }
+  const T* row = xc + (int64_t)h * W;
+  seg[0] = hasl ? (float)row[-1] : 0.f;
+  ld8f(row, seg + 1);
+  seg[9] = hasr ? (float)row[8] : 0.f;
+}
+
+// avg pool k3 s1 p1: nine taps per output summed kh-major, kw-minor in
+// fp32, one division by the generic kernel's avg_div.
+template <typename T>
+__global__ void __launch_bounds__(256)
+avgpool3s1_fwd_vec(const T* __restrict__ x, T* __restrict__ y, int64_t NC,
+                   int H, int W, long gr0, long gc0, long Hg, long Wg,
+                   int include_pad) {
+  const int CH = W >> 3;
+  const int NS = (H + POOL_R - 1) / POOL_R;
+  const int64_t total = NC * NS * CH;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += stride) {
+    const int c = (int)(t % CH);
+    const int64_t q = t / CH;
+    const int oh0 = (int)(q % NS) * POOL_R;
+    const int64_t plane = q / NS;
+    const T* xc = x + plane * H * W + c * 8;
+    T* yc = y + plane * H * W + c * 8;
+    const bool hasl = c > 0, hasr = c < CH - 1;
+    // every window of this chunk lies inside the global image column-wise
+    const bool col_in = (gc0 + c * 8) >= 0 && (gc0 + c * 8 + 7 + 3) <= Wg;
+    float s0[10], s1[10], s2[10];
+    avg_row<T>(xc, oh0 - 1, H, W, hasl, hasr, s0);
+    avg_row<T>(xc, oh0, H, W, hasl, hasr, s1);
+#pragma unroll
+    for (int r = 0; r < POOL_R; ++r) {
+      const int oh = oh0 + r;
+      if (oh >= H) break;
+      avg_row<T>(xc, oh + 1, H, W, hasl, hasr, s2);
+      float dv[8];
+      if (include_pad || (col_in && (gr0 + oh) >= 0 && (gr0 + oh + 3) <= Hg)) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dv[e] = 9.f;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          dv[e] = avg_div(oh, c * 8 + e, 1, 3, gr0, gc0, Hg, Wg, 0);
+      }
+      float out[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a += s0[e + j];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a += s1[e + j];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a += s2[e + j];
+        out[e] = a / dv[e];
+      }
+      st8f(yc + (int64_t)oh * W, out);
+#pragma unroll
+      for (int j = 0; j < 10; ++j) { s0[j] = s1[j]; s1[j] = s2[j]; }
+    }
+  }
+}
+
+// One go row for the avg backward in both scalings the generic kernel
+// can apply: gm = g * (1/9) (what an interior thread uses) and, only when
+// this strip has a non-interior thread-row (need_div), gd = g / avg_div.
+template <typename T>
+__device__ __forceinline__ void avg_go_row(const T* __restrict__ gc, int oh,
+                                           int H, int W, int c, bool hasl,
+                                           bool hasr, bool need_div, long gr0,
+                                           long gc0, long Hg, long Wg,
+                                           float* gm, float* gd) {
+  float g[10];
+  avg_row<T>(gc, oh, H, W, hasl, hasr, g);
+  const float inv_kk = 1.f / 9.f;
+#pragma unroll
+  for (int j = 0; j < 10; ++j) { gm[j] = g[j] * inv_kk; gd[j] = 0.f; }
+  if (need_div && oh >= 0 && oh < H) {
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {
+      const int ow = c * 8 - 1 + j;
+      if (ow >= 0 && ow < W)
+        gd[j] = g[j] / avg_div(oh, ow, 1, 3, gr0, gc0, Hg, Wg, 0);
+    }
+  }
+}
+
+// avg pool backward k3 s1 p1. Keeps the generic <3,1> arithmetic: per go
+// row a three-tap `sum` in ascending ow, then acc += sum in ascending oh;
+// the scaling is g * (1/9) when the thread-row is interior (judged on the
+// same clipped candidate ranges) and g / avg_div otherwise.
+template <typename T>
+__global__ void __launch_bounds__(256)
+avgpool3s1_bwd_vec(const T* __restrict__ go, T* __restrict__ gi, int64_t NC,
+                   int H, int W, long gr0, long gc0, long Hg, long Wg,
+                   int include_pad, int64_t C, int64_t go_bs) {
+  const int CH = W >> 3;
+  const int NS = (H + POOL_R - 1) / POOL_R;
+  const int64_t total = NC * NS * CH;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += stride) {
+    const int c = (int)(t % CH);
+    const int64_t q = t / CH;
+    const int h0 = (int)(q % NS) * POOL_R;
+    const int64_t plane = q / NS;
+    const int64_t HW = (int64_t)H * W;
+    const T* gc = go + (plane / C) * go_bs + (plane % C) * HW + c * 8;
+    T* gic = gi + plane * HW + c * 8;
+    const bool hasl = c > 0, hasr = c < CH - 1;
+    const int ow_lo = hasl ? c * 8 - 1 : 0;
+    const int ow_hi = hasr ? c * 8 + 8 : W - 1;
+    const bool col_in = (gc0 + ow_lo) >= 0 && (gc0 + ow_hi + 3) <= Wg;
+    // rows h0-1 .. h0+R clipped to the plane bound every candidate range
+    // of this strip; if they are all inside the image no thread-row of the
+    // strip needs the division
+    const int r_lo = h0 > 0 ? h0 - 1 : 0;
+    const int r_hi = h0 + POOL_R < H ? h0 + POOL_R : H - 1;
+    const bool need_div =
+        !include_pad &&
+        !(col_in && (gr0 + r_lo) >= 0 && (gr0 + r_hi + 3) <= Hg);
+    float m0[10], m1[10], m2[10], d0[10], d1[10], d2[10];
+    avg_go_row<T>(gc, h0 - 1, H, W, c, hasl, hasr, need_div, gr0, gc0, Hg, Wg,
+                  m0, d0);
+    avg_go_row<T>(gc, h0, H, W, c, hasl, hasr, need_div, gr0, gc0, Hg, Wg, m1,
+                  d1);
+#pragma unroll
+    for (int r = 0; r < POOL_R; ++r) {
+      const int h = h0 + r;
+      if (h >= H) break;
+      avg_go_row<T>(gc, h + 1, H, W, c, hasl, hasr, need_div, gr0, gc0, Hg, Wg,
+                    m2, d2);
+      const int oh_lo = h > 0 ? h - 1 : 0;
+      const int oh_hi = h + 1 < H ? h + 1 : H - 1;
+      const bool interior =
+          include_pad ||
+          (col_in && (gr0 + oh_lo) >= 0 && (gr0 + oh_hi + 3) <= Hg);
+      float acc[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float a = 0.f;
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s += interior ? m0[e + j] : d0[e + j];
+        a += s;
+        s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s += interior ? m1[e + j] : d1[e + j];
+        a += s;
+        s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s += interior ? m2[e + j] : d2[e + j];
+        a += s;
+        acc[e] = a;
+      }
+      st8f(gic + (int64_t)h * W, acc);
+#pragma unroll
+      for (int j = 0; j < 10; ++j) {
+        m0[j] = m1[j]; d0[j] = d1[j];
+        m1[j] = m2[j]; d1[j] = d2[j];
+      }
+    }
   }
 }
 
@@ -857,9 +1422,121 @@ static inline int grid_for(int64_t total, int block) {
   return (int)std::min<int64_t>(g, 4096);
 }
 
+// grid for the *_vec pool kernels: one thread per (plane, strip, chunk)
+static inline int pool_vec_grid(int64_t threads) {
+  return (int)std::min<int64_t>((threads + 255) / 256, 1 << 20);
+}
+
+static inline int64_t pool_strips(int64_t rows) {
+  return (rows + POOL_R - 1) / POOL_R;
+}
+
+static inline bool aligned16(const void* p) {
+  return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+}
+
+// Shape half of the fast-path predicate: 2-byte dtype, whole 16-byte
+// chunks on both sides, and (H, W) <-> (OH, OW) consistent with (k,s,p).
+static bool pool_vec_shape_ok(at::ScalarType st, int64_t H, int64_t W,
+                              int64_t OH, int64_t OW, int64_t k, int64_t s,
+                              int64_t p) {
+  const bool geom = (k == 3 && s == 1 && p == 1) ||
+                    (k == 3 && s == 2 && p == 1) ||
+                    (k == 2 && s == 2 && p == 0);
+  if (!geom) return false;
+  if (st != at::ScalarType::Half && st != at::ScalarType::BFloat16)
+    return false;
+  if (H < 1 || W < 8 || OH < 1 || OW < 8 || W % 8 != 0 || OW % 8 != 0)
+    return false;
+  if (OH != (H + 2 * p - k) / s + 1 || OW != (W + 2 * p - k) / s + 1)
+    return false;
+  if (s == 2 && W != 2 * OW) return false;
+  return H * W < (int64_t(1) << 30);
+}
+
+// A 4-D gradient that is a channel slice of a contiguous NCHW tensor:
+// dense planes, dense channels, free batch stride.
+static bool go_plane_dense(const torch::Tensor& go) {
+  return go.dim() == 4 && go.stride(3) == 1 && go.stride(2) == go.size(3) &&
+         go.stride(1) == go.size(2) * go.size(3) && go.stride(0) >= 0;
+}
+
+// Launchers for the *_vec kernels; only 2-byte dtypes instantiate them
+// (the host predicate never selects them for anything else).
+template <typename T>
+void maxpool_fwd_vec(const T* x, T* y, uint8_t* idx, int64_t NC, int H, int W,
+                     int OH, int OW, int k, int s, hipStream_t stream) {
+  if constexpr (sizeof(T) == 2) {
+    const dim3 grid(pool_vec_grid(NC * pool_strips(OH) * (OW / 8)));
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, x, y, idx, NC, H,
+                         W, OH, OW);
+    };
+    if (k == 2) launch(maxpool2s2_fwd_vec<T>);
+    else if (s == 1) launch(maxpool3_fwd_vec<T, 1>);
+    else launch(maxpool3_fwd_vec<T, 2>);
+  } else {
+    TORCH_CHECK(false, "pool fast path needs a 2-byte dtype");
+  }
+}
+
+template <typename T>
+void maxpool_bwd_vec(const T* go, const uint8_t* idx, T* gi, int64_t NC, int H,
+                     int W, int OH, int OW, int k, int s, int64_t C,
+                     int64_t go_bs, hipStream_t stream) {
+  if constexpr (sizeof(T) == 2) {
+    const int64_t chunks = s == 1 ? W / 8 : W / 16;
+    const int64_t rows = s == 1 ? H : (H + 1) / 2;
+    const dim3 grid(pool_vec_grid(NC * pool_strips(rows) * chunks));
+    if (s == 1) {
+      hipLaunchKernelGGL(maxpool3s1_bwd_vec<T>, grid, dim3(256), 0, stream, go,
+                         idx, gi, NC, H, W, C, go_bs);
+    } else {
+      auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, go, idx, gi, NC,
+                           H, W, OH, OW, C, go_bs);
+      };
+      if (k == 3) launch(maxpool3s2_bwd_vec<T>);
+      else launch(maxpool2s2_bwd_vec<T>);
+    }
+  } else {
+    TORCH_CHECK(false, "pool fast path needs a 2-byte dtype");
+  }
+}
+
+template <typename T>
+void avgpool_fwd_vec(const T* x, T* y, int64_t NC, int H, int W, int64_t gr0,
+                     int64_t gc0, int64_t Hg, int64_t Wg, bool include_pad,
+                     hipStream_t stream) {
+  if constexpr (sizeof(T) == 2) {
+    const dim3 grid(pool_vec_grid(NC * pool_strips(H) * (W / 8)));
+    hipLaunchKernelGGL(avgpool3s1_fwd_vec<T>, grid, dim3(256), 0, stream, x, y,
+                       NC, H, W, (long)gr0, (long)gc0, (long)Hg, (long)Wg,
+                       include_pad ? 1 : 0);
+  } else {
+    TORCH_CHECK(false, "pool fast path needs a 2-byte dtype");
+  }
+}
+
+template <typename T>
+void avgpool_bwd_vec(const T* go, T* gi, int64_t NC, int H, int W, int64_t gr0,
+                     int64_t gc0, int64_t Hg, int64_t Wg, bool include_pad,
+                     int64_t C, int64_t go_bs, hipStream_t stream) {
+  if constexpr (sizeof(T) == 2) {
+    const dim3 grid(pool_vec_grid(NC * pool_strips(H) * (W / 8)));
+    hipLaunchKernelGGL(avgpool3s1_bwd_vec<T>, grid, dim3(256), 0, stream, go,
+                       gi, NC, H, W, (long)gr0, (long)gc0, (long)Hg, (long)Wg,
+                       include_pad ? 1 : 0, C, go_bs);
+  } else {
+    TORCH_CHECK(false, "pool fast path needs a 2-byte dtype");
+  }
+}
+
 std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k, int64_t s,
-                                       int64_t p) {
+                                       int64_t p, bool force_generic) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
+  TORCH_CHECK(k * k <= 256,
+              "maxpool_fwd: k*k must fit the u8 window index, got k=", k);
   const int64_t N = x.size(0), C = x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
   const int OH = (H + 2 * (int)p - (int)k) / (int)s + 1;
@@ -868,9 +1545,20 @@ std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k, int64_t s,
   auto idx = torch::empty({N, C, OH, OW}, x.options().dtype(torch::kByte));
   const int64_t total = N * C * (int64_t)OH * OW;
   auto stream = at::cuda::getCurrentCUDAStream();
+  const bool fast = !force_generic && total > 0 &&
+                    pool_vec_shape_ok(x.scalar_type(), H, W, OH, OW, k, s, p) &&
+                    aligned16(x.data_ptr()) && aligned16(y.data_ptr()) &&
+                    aligned16(idx.data_ptr());
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
       "maxpool_fwd", [&] {
+        if (fast) {
+          maxpool_fwd_vec<scalar_t>(x.data_ptr<scalar_t>(),
+                                    y.data_ptr<scalar_t>(),
+                                    idx.data_ptr<uint8_t>(), N * C, H, W, OH, OW,
+                                    (int)k, (int)s, stream.stream());
+          return;
+        }
         auto launch = [&](auto kernel) {
           hipLaunchKernelGGL(kernel, dim3(grid_for(total, 256)), dim3(256), 0,
                              stream.stream(), x.data_ptr<scalar_t>(),
@@ -890,22 +1578,43 @@ std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k, int64_t s,
 }
 
 torch::Tensor maxpool_bwd(torch::Tensor go, torch::Tensor idx, int64_t H,
-                          int64_t W, int64_t k, int64_t s, int64_t p) {
-  TORCH_CHECK(go.is_cuda() && go.is_contiguous());
+                          int64_t W, int64_t k, int64_t s, int64_t p,
+                          bool force_generic) {
+  const bool go_contig = go.dim() == 4 && go.is_contiguous();
+  TORCH_CHECK(go.is_cuda() && (go_contig || go_plane_dense(go)),
+              "maxpool_bwd: go must be a channel slice of a contiguous NCHW "
+              "tensor");
+  TORCH_CHECK(k * k <= 256,
+              "maxpool_bwd: k*k must fit the u8 window index, got k=", k);
+  TORCH_CHECK(idx.is_cuda() && idx.is_contiguous() &&
+              idx.scalar_type() == torch::kByte && idx.numel() == go.numel());
   const int64_t N = go.size(0), C = go.size(1);
   const int OH = (int)go.size(2), OW = (int)go.size(3);
+  const int64_t go_bs = go_contig ? C * OH * OW : go.stride(0);
   auto gi = torch::empty({N, C, H, W}, go.options());
   const int64_t total = N * C * H * W;
   auto stream = at::cuda::getCurrentCUDAStream();
+  const bool fast = !force_generic && total > 0 && go.numel() > 0 &&
+                    pool_vec_shape_ok(go.scalar_type(), H, W, OH, OW, k, s, p) &&
+                    go_bs % 8 == 0 && aligned16(go.data_ptr()) &&
+                    aligned16(idx.data_ptr()) && aligned16(gi.data_ptr());
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, go.scalar_type(),
       "maxpool_bwd", [&] {
+        if (fast) {
+          maxpool_bwd_vec<scalar_t>(go.data_ptr<scalar_t>(),
+                                    idx.data_ptr<uint8_t>(),
+                                    gi.data_ptr<scalar_t>(), N * C, (int)H,
+                                    (int)W, OH, OW, (int)k, (int)s, C, go_bs,
+                                    stream.stream());
+          return;
+        }
         auto launch = [&](auto kernel) {
           hipLaunchKernelGGL(kernel, dim3(grid_for(total, 256)), dim3(256), 0,
                              stream.stream(), go.data_ptr<scalar_t>(),
                              idx.data_ptr<uint8_t>(), gi.data_ptr<scalar_t>(),
                              N * C, (int)H, (int)W, OH, OW, (int)k, (int)s,
-                             (int)p);
+                             (int)p, C, go_bs);
         };
         if (k == 3 && s == 1)
           launch(maxpool_bwd_kernel<scalar_t, 3, 1>);
@@ -921,7 +1630,7 @@ torch::Tensor maxpool_bwd(torch::Tensor go, torch::Tensor idx, int64_t H,
 
 torch::Tensor avgpool_fwd(torch::Tensor x, int64_t k, int64_t s, int64_t p,
                           int64_t gr0, int64_t gc0, int64_t Hg, int64_t Wg,
-                          bool include_pad) {
+                          bool include_pad, bool force_generic) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
   const int64_t N = x.size(0), C = x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
@@ -930,9 +1639,18 @@ torch::Tensor avgpool_fwd(torch::Tensor x, int64_t k, int64_t s, int64_t p,
   auto y = torch::empty({N, C, OH, OW}, x.options());
   const int64_t total = N * C * (int64_t)OH * OW;
   auto stream = at::cuda::getCurrentCUDAStream();
+  const bool fast = !force_generic && total > 0 && k == 3 && s == 1 &&
+                    pool_vec_shape_ok(x.scalar_type(), H, W, OH, OW, k, s, p) &&
+                    aligned16(x.data_ptr()) && aligned16(y.data_ptr());
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
       "avgpool_fwd", [&] {
+        if (fast) {
+          avgpool_fwd_vec<scalar_t>(x.data_ptr<scalar_t>(),
+                                    y.data_ptr<scalar_t>(), N * C, H, W, gr0,
+                                    gc0, Hg, Wg, include_pad, stream.stream());
+          return;
+        }
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, dim3(grid_for(total, 256)), dim3(256), 0,
                              stream.stream(), x.data_ptr<scalar_t>(),
@@ -949,23 +1667,40 @@ torch::Tensor avgpool_fwd(torch::Tensor x, int64_t k, int64_t s, int64_t p,
 
 torch::Tensor avgpool_bwd(torch::Tensor go, int64_t H, int64_t W, int64_t k,
                           int64_t s, int64_t p, int64_t gr0, int64_t gc0,
-                          int64_t Hg, int64_t Wg, bool include_pad) {
-  TORCH_CHECK(go.is_cuda() && go.is_contiguous());
+                          int64_t Hg, int64_t Wg, bool include_pad,
+                          bool force_generic) {
+  const bool go_contig = go.dim() == 4 && go.is_contiguous();
+  TORCH_CHECK(go.is_cuda() && (go_contig || go_plane_dense(go)),
+              "avgpool_bwd: go must be a channel slice of a contiguous NCHW "
+              "tensor");
   const int64_t N = go.size(0), C = go.size(1);
   const int OH = (int)go.size(2), OW = (int)go.size(3);
+  const int64_t go_bs = go_contig ? C * OH * OW : go.stride(0);
   auto gi = torch::empty({N, C, H, W}, go.options());
   const int64_t total = N * C * H * W;
   auto stream = at::cuda::getCurrentCUDAStream();
+  const bool fast = !force_generic && total > 0 && go.numel() > 0 && k == 3 &&
+                    s == 1 &&
+                    pool_vec_shape_ok(go.scalar_type(), H, W, OH, OW, k, s, p) &&
+                    go_bs % 8 == 0 && aligned16(go.data_ptr()) &&
+                    aligned16(gi.data_ptr());
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, go.scalar_type(),
       "avgpool_bwd", [&] {
+        if (fast) {
+          avgpool_bwd_vec<scalar_t>(go.data_ptr<scalar_t>(),
+                                    gi.data_ptr<scalar_t>(), N * C, (int)H,
+                                    (int)W, gr0, gc0, Hg, Wg, include_pad, C,
+                                    go_bs, stream.stream());
+          return;
+        }
         auto launch = [&](auto kern) {
           hipLaunchKernelGGL(kern, dim3(grid_for(total, 256)), dim3(256), 0,
                              stream.stream(), go.data_ptr<scalar_t>(),
                              gi.data_ptr<scalar_t>(), N * C, (int)H, (int)W,
                              OH, OW, (int)k, (int)s, (int)p, (long)gr0,
                              (long)gc0, (long)Hg, (long)Wg,
-                             include_pad ? 1 : 0);
+                             include_pad ? 1 : 0, C, go_bs);
         };
         if (k == 3 && s == 2) launch(avgpool_bwd_kernel<scalar_t, 3, 2>);
         else if (k == 3 && s == 1) launch(avgpool_bwd_kernel<scalar_t, 3, 1>);
@@ -1130,10 +1865,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("halo_unpack", &halo_copy<1>, "unpack halo strips buffer->tile");
   m.def("halo_unpack_add", &halo_copy<2>, "accumulate grad strips into tile");
   m.def("bn_stats", &bn_stats, "per-channel [sum, sumsq] in one pass");
-  m.def("maxpool_fwd", &maxpool_fwd);
-  m.def("maxpool_bwd", &maxpool_bwd);
-  m.def("avgpool_fwd", &avgpool_fwd);
-  m.def("avgpool_bwd", &avgpool_bwd);
+  namespace py = pybind11;
+  m.def("maxpool_fwd", &maxpool_fwd, py::arg("x"), py::arg("k"), py::arg("s"),
+        py::arg("p"), py::arg("force_generic") = false);
+  m.def("maxpool_bwd", &maxpool_bwd, py::arg("go"), py::arg("idx"),
+        py::arg("H"), py::arg("W"), py::arg("k"), py::arg("s"), py::arg("p"),
+        py::arg("force_generic") = false);
+  m.def("avgpool_fwd", &avgpool_fwd, py::arg("x"), py::arg("k"), py::arg("s"),
+        py::arg("p"), py::arg("gr0"), py::arg("gc0"), py::arg("Hg"),
+        py::arg("Wg"), py::arg("include_pad"),
+        py::arg("force_generic") = false);
+  m.def("avgpool_bwd", &avgpool_bwd, py::arg("go"), py::arg("H"), py::arg("W"),
+        py::arg("k"), py::arg("s"), py::arg("p"), py::arg("gr0"),
+        py::arg("gc0"), py::arg("Hg"), py::arg("Wg"), py::arg("include_pad"),
+        py::arg("force_generic") = false);
   m.def("bn_stats64", &bn_stats64);
   m.def("bn_apply", &bn_apply);
   m.def("bn_bwd_stats", &bn_bwd_stats);

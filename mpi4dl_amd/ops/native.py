@@ -14,6 +14,19 @@ import torch.distributed as dist
 from . import backend
 
 
+def _plane_dense(go):
+    """go as the pool backward kernels take it: a channel slice of a
+    contiguous NCHW tensor (dense planes and channels, any batch stride).
+    Anything else is repacked."""
+    if go.is_contiguous():
+        return go
+    _, _, oh, ow = go.shape
+    st = go.stride()
+    if st[3] == 1 and st[2] == ow and st[1] == oh * ow and st[0] >= 0:
+        return go
+    return go.contiguous()
+
+
 class MaxPool2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, k, s, p):
@@ -28,7 +41,7 @@ class MaxPool2dFn(torch.autograd.Function):
     def backward(ctx, go):
         (idx,) = ctx.saved_tensors
         H, W, k, s, p = ctx.geom
-        gi = backend.ext().maxpool_bwd(go.contiguous(), idx, H, W, k, s, p)
+        gi = backend.ext().maxpool_bwd(_plane_dense(go), idx, H, W, k, s, p)
         return gi, None, None, None
 
 
@@ -49,7 +62,7 @@ class AvgPool2dFn(torch.autograd.Function):
     def backward(ctx, go):
         H, W, k, s, p, gr0, gc0, Hg, Wg, include_pad = ctx.geom
         gi = backend.ext().avgpool_bwd(
-            go.contiguous(), H, W, k, s, p, gr0, gc0, Hg, Wg, include_pad
+            _plane_dense(go), H, W, k, s, p, gr0, gc0, Hg, Wg, include_pad
         )
         return (gi,) + (None,) * 8
 
