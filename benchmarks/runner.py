@@ -69,9 +69,15 @@ def build_model(args, plan, mb):
             num_filters=args.num_filters if args.num_filters <= 64 else 16,
             plan=plan, ref_stem=args.ref_stem,
         )
+    layers = args.num_layers - (args.num_layers % 3) or 3
+    if args.halo_d2:
+        from mpi4dl_amd.models.amoebanet_d2 import amoebanetd_d2
+
+        return amoebanetd_d2(args.num_classes, layers, args.num_filters,
+                             plan=plan,
+                             ref_quirks=getattr(args, "ref_quirks", False))
     from mpi4dl_amd.models.amoebanet import amoebanetd
 
-    layers = args.num_layers - (args.num_layers % 3) or 3
     return amoebanetd(args.num_classes, layers, args.num_filters, plan=plan,
                       ref_quirks=getattr(args, "ref_quirks", False))
 

@@ -1322,6 +1322,296 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ go,
 }
 
 // ---------------------------------------------------------------------------
+// Ragged / region BatchNorm kernels: any H, W (surplus tiles of the D2
+// fused-halo design are e.g. 259x259) and statistics restricted to a
+// region = rows [top, H-bottom) x cols [left, W-right) of every plane.
+//
+// All of them walk 16-byte SLOTS of the flat tensor (the tensor base is
+// 16-byte aligned — enforced host-side), so every vector access is
+// aligned whatever the row / plane start is. The reductions load a whole
+// slot wherever it lies inside the tensor and mask the elements outside
+// their range (head and tail of a row or plane); the elementwise kernels
+// resolve a slot that straddles a plane seam per element.
+// ---------------------------------------------------------------------------
+
+// [sum, sumsq] of the elements of slot [v0, v0+VEC) that lie in [a, e).
+template <typename T>
+__device__ __forceinline__ void stats_slot(const T* __restrict__ x, int64_t v0,
+                                           int64_t a, int64_t e, int64_t numel,
+                                           double& s, double& ss) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int lo = (int)max(a - v0, (int64_t)0);
+  const int hi = (int)min(e - v0, (int64_t)VEC);
+  if (v0 + VEC <= numel) {
+    const uint4 raw = *(const uint4*)(x + v0);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      float f = to_f32(((const T*)&raw)[k]);
+      f = (k >= lo && k < hi) ? f : 0.f;
+      s += (double)f;
+      ss += (double)(f * f);
+    }
+  } else {
+    for (int k = lo; k < hi; ++k) {
+      const float f = to_f32(x[v0 + k]);
+      s += (double)f;
+      ss += (double)(f * f);
+    }
+  }
+}
+
+// block-wide sum of (s, ss) into out[ch], out[C + ch]: one fp64 atomicAdd
+// per block per output
+__device__ __forceinline__ void stats_block_commit(double s, double ss,
+                                                   double* __restrict__ out,
+                                                   int64_t C, int64_t ch) {
+  for (int off = 32; off > 0; off >>= 1) {
+    s += __shfl_down(s, off, 64);
+    ss += __shfl_down(ss, off, 64);
+  }
+  __shared__ double ls[8], lss[8];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) { ls[wid] = s; lss[wid] = ss; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ts = 0.0, tss = 0.0;
+    for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) { ts += ls[wv]; tss += lss[wv]; }
+    atomicAdd(&out[ch], ts);
+    atomicAdd(&out[C + ch], tss);
+  }
+}
+
+// j / d for j * d < 2^32 with m = 2^32 / d + 1 (host-checked)
+__device__ __forceinline__ uint32_t fast_div(uint32_t j, uint32_t d,
+                                             uint32_t m) {
+  return d == 1 ? j : __umulhi(j, m);
+}
+
+// Contiguous range [start, start+total) of every plane (a region whose
+// rows are full width). 2D grid: x = channel, y = chunk; the chunk
+// windows start at the plane range's first SLOT, so every block walks
+// chunk/VEC whole slots whatever the plane's alignment.
+template <typename T>
+__global__ void bn_stats64_span_kernel(const T* __restrict__ x,
+                                       double* __restrict__ out, int64_t N,
+                                       int64_t C, int64_t HW, int64_t start,
+                                       int64_t total, int64_t chunk) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int64_t ch = blockIdx.x;
+  const int64_t numel = N * C * HW;
+  double s = 0.0, ss = 0.0;
+  for (int64_t n = 0; n < N; ++n) {
+    const int64_t a0 = (n * C + ch) * HW + start;
+    const int64_t w0 = a0 / VEC * VEC + (int64_t)blockIdx.y * chunk;
+    const int64_t a = max(a0, w0);
+    const int64_t e = min(a0 + total, w0 + chunk);
+    for (int64_t v0 = w0 + (int64_t)threadIdx.x * VEC; v0 < e;
+         v0 += (int64_t)blockDim.x * VEC)
+      stats_slot<T>(x, v0, a, e, numel, s, ss);
+  }
+  stats_block_commit(s, ss, out, C, ch);
+}
+
+// Region with a left/right margin: rows of `len` elements, `W` apart,
+// the first `start` into each plane. 2D grid: x = channel, y = block of
+// `rpc` rows; the (image, row, slot) triples of a block are dealt to its
+// threads as one flat index.
+template <typename T>
+__global__ void bn_stats64_region_kernel(const T* __restrict__ x,
+                                         double* __restrict__ out, int64_t N,
+                                         int64_t C, int64_t HW, int64_t start,
+                                         int len, int W, int nrows, int rpc,
+                                         uint32_t S, uint32_t mS) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int64_t ch = blockIdx.x;
+  const int64_t numel = N * C * HW;
+  const int r0 = (int)blockIdx.y * rpc;
+  const uint32_t rows = (uint32_t)(min(r0 + rpc, nrows) - r0);
+  const uint32_t mR = (uint32_t)(((uint64_t)1 << 32) / rows + 1);
+  const uint32_t work = (uint32_t)N * rows * S;
+  double s = 0.0, ss = 0.0;
+  for (uint32_t j = threadIdx.x; j < work; j += blockDim.x) {
+    const uint32_t q = fast_div(j, S, mS);     // image * rows + row
+    const uint32_t sl = j - q * S;             // slot within the row
+    const uint32_t n = fast_div(q, rows, mR);
+    const uint32_t r = q - n * rows;
+    const int64_t a =
+        ((int64_t)n * C + ch) * HW + start + (int64_t)(r0 + (int)r) * W;
+    const int64_t e = a + len;
+    const int64_t v0 = (a / VEC + sl) * VEC;
+    if (v0 < e) stats_slot<T>(x, v0, a, e, numel, s, ss);
+  }
+  stats_block_commit(s, ss, out, C, ch);
+}
+
+// bn_apply_kernel for any HW: a slot inside one plane takes its channel
+// once; a slot across a plane seam or the flat tail goes per element.
+template <typename T, bool RELU>
+__global__ void bn_apply_ragged_kernel(const T* __restrict__ x,
+                                       T* __restrict__ y,
+                                       const float* __restrict__ mean,
+                                       const float* __restrict__ invstd,
+                                       const float* __restrict__ wgt,
+                                       const float* __restrict__ bias,
+                                       int64_t total, int64_t C, int64_t HW) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int64_t nvec = (total + VEC - 1) / VEC;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t iv = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; iv < nvec;
+       iv += stride) {
+    const int64_t i = iv * VEC;
+    const int64_t p0 = i / HW;
+    if (i + VEC <= total && i - p0 * HW + VEC <= HW) {
+      const int64_t ch = p0 % C;
+      const float m = mean[ch], inv = invstd[ch], w = wgt[ch], b = bias[ch];
+      const uint4 rx = *(const uint4*)(x + i);
+      uint4 ry;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        float v = (to_f32(((const T*)&rx)[e]) - m) * inv * w + b;
+        if (RELU) v = v > 0.f ? v : 0.f;
+        ((T*)&ry)[e] = (T)v;
+      }
+      *(uint4*)(y + i) = ry;
+    } else {
+      const int64_t k1 = min(i + VEC, total);
+      for (int64_t k = i; k < k1; ++k) {
+        const int64_t ch = (k / HW) % C;
+        float v = (to_f32(x[k]) - mean[ch]) * invstd[ch] * wgt[ch] + bias[ch];
+        if (RELU) v = v > 0.f ? v : 0.f;
+        y[k] = (T)v;
+      }
+    }
+  }
+}
+
+// bn_bwd_stats_kernel for any HW: block (ch, y) sums one chunk of every
+// image's plane; chunk windows start at the plane's first slot (see
+// bn_stats64_span_kernel), elements outside the plane are masked.
+template <typename T, bool RELU>
+__global__ void bn_bwd_stats_ragged_kernel(const T* __restrict__ go,
+                                           const T* __restrict__ x,
+                                           const T* __restrict__ y,
+                                           const float* __restrict__ mean,
+                                           const float* __restrict__ invstd,
+                                           double* __restrict__ out, int64_t N,
+                                           int64_t C, int64_t HW,
+                                           int64_t chunk) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int64_t ch = blockIdx.x;
+  const int64_t numel = N * C * HW;
+  const float m = mean[ch], inv = invstd[ch];
+  double gs = 0.0, gx = 0.0;
+  for (int64_t n = 0; n < N; ++n) {
+    const int64_t a0 = (n * C + ch) * HW;
+    const int64_t w0 = a0 / VEC * VEC + (int64_t)blockIdx.y * chunk;
+    const int64_t a = max(a0, w0);
+    const int64_t e = min(a0 + HW, w0 + chunk);
+    for (int64_t v0 = w0 + (int64_t)threadIdx.x * VEC; v0 < e;
+         v0 += (int64_t)blockDim.x * VEC) {
+      const int lo = (int)max(a - v0, (int64_t)0);
+      const int hi = (int)min(e - v0, (int64_t)VEC);
+      if (v0 + VEC <= numel) {
+        const uint4 rg = *(const uint4*)(go + v0);
+        const uint4 rx = *(const uint4*)(x + v0);
+        uint4 ry;
+        if (RELU) ry = *(const uint4*)(y + v0);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+          float g = to_f32(((const T*)&rg)[k]);
+          if (RELU && to_f32(((const T*)&ry)[k]) <= 0.f) g = 0.f;
+          const float xh = (to_f32(((const T*)&rx)[k]) - m) * inv;
+          const bool in = k >= lo && k < hi;
+          gs += (double)(in ? g : 0.f);
+          gx += (double)(in ? g * xh : 0.f);
+        }
+      } else {
+        for (int k = lo; k < hi; ++k) {
+          float g = to_f32(go[v0 + k]);
+          if (RELU && to_f32(y[v0 + k]) <= 0.f) g = 0.f;
+          const float xh = (to_f32(x[v0 + k]) - m) * inv;
+          gs += (double)g;
+          gx += (double)(g * xh);
+        }
+      }
+    }
+  }
+  stats_block_commit(gs, gx, out, C, ch);
+}
+
+// bn_bwd_apply_kernel for any HW. REGION: mean/var came from the region
+// pixels only while every pixel was normalised, so the two reduction
+// terms reach region pixels only:
+//   gi_p = w*inv*[g_p - 1{p in region}*(gsum/n + xhat_p*gxsum/n)]
+template <typename T, bool RELU, bool REGION>
+__global__ void bn_bwd_apply_ragged_kernel(
+    const T* __restrict__ go, const T* __restrict__ x, const T* __restrict__ y,
+    T* __restrict__ gi, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ wgt,
+    const float* __restrict__ gsum, const float* __restrict__ gxsum,
+    double inv_n, int64_t total, int64_t C, int64_t HW, int W, int row_lo,
+    int row_hi, int col_lo, int col_hi) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int64_t nvec = (total + VEC - 1) / VEC;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t iv = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; iv < nvec;
+       iv += stride) {
+    const int64_t i = iv * VEC;
+    const int64_t p0 = i / HW;
+    const int64_t rem = i - p0 * HW;
+    if (i + VEC <= total && rem + VEC <= HW) {
+      const int64_t ch = p0 % C;
+      const float m = mean[ch], inv = invstd[ch], w = wgt[ch];
+      const float gsn = (float)(gsum[ch] * inv_n);
+      const float gxn = (float)(gxsum[ch] * inv_n);
+      int row = 0, col = 0;
+      if (REGION) {
+        row = (int)(rem / W);
+        col = (int)(rem - (int64_t)row * W);
+      }
+      const uint4 rg = *(const uint4*)(go + i);
+      const uint4 rx = *(const uint4*)(x + i);
+      uint4 ry;
+      if (RELU) ry = *(const uint4*)(y + i);
+      uint4 ro;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        float g = to_f32(((const T*)&rg)[e]);
+        if (RELU && to_f32(((const T*)&ry)[e]) <= 0.f) g = 0.f;
+        const float xh = (to_f32(((const T*)&rx)[e]) - m) * inv;
+        float red = gsn + xh * gxn;
+        if (REGION) {
+          if (row < row_lo || row >= row_hi || col < col_lo || col >= col_hi)
+            red = 0.f;
+          if (++col == W) { col = 0; ++row; }
+        }
+        ((T*)&ro)[e] = (T)((g - red) * w * inv);
+      }
+      *(uint4*)(gi + i) = ro;
+    } else {
+      const int64_t k1 = min(i + VEC, total);
+      for (int64_t k = i; k < k1; ++k) {
+        const int64_t p = k / HW;
+        const int64_t ch = p % C;
+        const float inv = invstd[ch];
+        float g = to_f32(go[k]);
+        if (RELU && to_f32(y[k]) <= 0.f) g = 0.f;
+        const float xh = (to_f32(x[k]) - mean[ch]) * inv;
+        float red = (float)(gsum[ch] * inv_n) + xh * (float)(gxsum[ch] * inv_n);
+        if (REGION) {
+          const int64_t q = k - p * HW;
+          const int row = (int)(q / W);
+          const int col = (int)(q - (int64_t)row * W);
+          if (row < row_lo || row >= row_hi || col < col_lo || col >= col_hi)
+            red = 0.f;
+        }
+        gi[k] = (T)((g - red) * wgt[ch] * inv);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Fused momentum-SGD on flat fp32 buffers: one kernel for the whole
 // model step (replaces ~3 torch launches per parameter — the profile
 // showed 5.8k tiny CUDAFunctor_add kernels per step).
@@ -1760,14 +2050,103 @@ torch::Tensor bn_stats64_acc(torch::Tensor x, torch::Tensor out) {
   return out;
 }
 
+// the ragged kernels take 16-byte slots of the flat tensor from its base
+static torch::Tensor aligned16(const torch::Tensor& t) {
+  return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) ? t.clone() : t;
+}
+
+static void check_margin(const std::vector<int64_t>& mg, int64_t H,
+                         int64_t W) {
+  TORCH_CHECK(mg.size() == 4, "margin is (top, bottom, left, right)");
+  TORCH_CHECK(mg[0] >= 0 && mg[1] >= 0 && mg[2] >= 0 && mg[3] >= 0 &&
+                  mg[0] + mg[1] < H && mg[2] + mg[3] < W,
+              "margin leaves an empty region of a ", H, "x", W, " plane");
+}
+
+// bn_stats64_acc over the region only (margin = top, bottom, left, right).
+torch::Tensor bn_stats64_region_acc(torch::Tensor x, torch::Tensor out,
+                                    std::vector<int64_t> margin) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t HW = H * W;
+  check_margin(margin, H, W);
+  const int64_t mt = margin[0], mb = margin[1], ml = margin[2], mr = margin[3];
+  if (mt + mb + ml + mr == 0 && HW % 8 == 0) return bn_stats64_acc(x, out);
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+              out.scalar_type() == torch::kDouble && out.numel() == 2 * C);
+  TORCH_CHECK(HW < (int64_t)1 << 30, "plane too large");
+  x = aligned16(x);
+  const int64_t splits = stats_splits(C, HW);
+  int64_t chunk = (HW + splits - 1) / splits;
+  chunk = ((chunk + 2047) / 2048) * 2048;
+  const int64_t Hr = H - mt - mb;
+  const int vec = 16 / (int)x.element_size();
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (ml + mr == 0) {
+    // full-width rows: one contiguous range per plane
+    const int64_t start = mt * W, total = Hr * W;
+    const int64_t gy = (total + vec - 1 + chunk - 1) / chunk;
+    AT_DISPATCH_FLOATING_TYPES_AND2(
+        at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
+        "bn_stats64_span", [&] {
+          hipLaunchKernelGGL((bn_stats64_span_kernel<scalar_t>),
+                             dim3((uint32_t)C, (uint32_t)gy), dim3(256), 0,
+                             stream.stream(), x.data_ptr<scalar_t>(),
+                             out.data_ptr<double>(), N, C, HW, start, total,
+                             chunk);
+        });
+    return out;
+  }
+  const int64_t len = W - ml - mr;
+  const int64_t gy0 = (HW + chunk - 1) / chunk;
+  const int64_t rpc = (Hr + gy0 - 1) / gy0;
+  const int64_t gy = (Hr + rpc - 1) / rpc;
+  const int64_t S = len / vec + 2;  // slots a row can touch, at most
+  // fast_div's exactness bound for both of the kernel's divisions
+  TORCH_CHECK(N * rpc * S * std::max(S, rpc) < ((int64_t)1 << 32),
+              "bn_stats64_region_acc: batch x rows x width too large");
+  const uint32_t mS = (uint32_t)((((uint64_t)1) << 32) / (uint64_t)S + 1);
+  AT_DISPATCH_FLOATING_TYPES_AND2(
+      at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
+      "bn_stats64_region_acc", [&] {
+        hipLaunchKernelGGL((bn_stats64_region_kernel<scalar_t>),
+                           dim3((uint32_t)C, (uint32_t)gy), dim3(256), 0,
+                           stream.stream(), x.data_ptr<scalar_t>(),
+                           out.data_ptr<double>(), N, C, HW, mt * W + ml,
+                           (int)len, (int)W, (int)Hr, (int)rpc, (uint32_t)S,
+                           mS);
+      });
+  return out;
+}
+
 torch::Tensor bn_apply(torch::Tensor x, torch::Tensor mean,
                        torch::Tensor invstd, torch::Tensor w, torch::Tensor b,
                        bool relu) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
-  auto y = torch::empty_like(x);
   const int64_t total = N * C * HW;
   auto stream = at::cuda::getCurrentCUDAStream();
+  if (HW % 8 != 0) {
+    x = aligned16(x);
+    auto y = torch::empty_like(x);
+    const int vec = 16 / (int)x.element_size();
+    AT_DISPATCH_FLOATING_TYPES_AND2(
+        at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
+        "bn_apply_ragged", [&] {
+          auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(
+                kern, dim3(grid_for((total + vec - 1) / vec, 256)), dim3(256),
+                0, stream.stream(), x.data_ptr<scalar_t>(),
+                y.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+                invstd.data_ptr<float>(), w.data_ptr<float>(),
+                b.data_ptr<float>(), total, C, HW);
+          };
+          if (relu) launch(bn_apply_ragged_kernel<scalar_t, true>);
+          else launch(bn_apply_ragged_kernel<scalar_t, false>);
+        });
+    return y;
+  }
+  auto y = torch::empty_like(x);
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
       "bn_apply", [&] {
@@ -1799,6 +2178,33 @@ torch::Tensor bn_bwd_stats(torch::Tensor go, torch::Tensor x, torch::Tensor y,
   chunk = ((chunk + 2047) / 2048) * 2048;
   const int64_t gy = (HW + chunk - 1) / chunk;
   auto stream = at::cuda::getCurrentCUDAStream();
+  if (HW % 8 != 0) {
+    TORCH_CHECK(go.is_contiguous() && x.is_contiguous() &&
+                (!relu || y.is_contiguous()));
+    go = aligned16(go);
+    x = aligned16(x);
+    if (relu) y = aligned16(y);
+    // chunk windows start at the plane's first slot: up to vec-1 elements
+    // before the plane
+    const int64_t vec = 16 / (int64_t)x.element_size();
+    const int64_t gyr = (HW + vec - 1 + chunk - 1) / chunk;
+    AT_DISPATCH_FLOATING_TYPES_AND2(
+        at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
+        "bn_bwd_stats_ragged", [&] {
+          auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(
+                kern, dim3((uint32_t)C, (uint32_t)gyr), dim3(256), 0,
+                stream.stream(), go.data_ptr<scalar_t>(),
+                x.data_ptr<scalar_t>(),
+                relu ? y.data_ptr<scalar_t>() : (scalar_t*)nullptr,
+                mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                out.data_ptr<double>(), N, C, HW, chunk);
+          };
+          if (relu) launch(bn_bwd_stats_ragged_kernel<scalar_t, true>);
+          else launch(bn_bwd_stats_ragged_kernel<scalar_t, false>);
+        });
+    return out;
+  }
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
       "bn_bwd_stats", [&] {
@@ -1820,11 +2226,59 @@ torch::Tensor bn_bwd_stats(torch::Tensor go, torch::Tensor x, torch::Tensor y,
   return out;
 }
 
+// any-HW backward apply; `region` restricts the two reduction terms to
+// rows [row_lo,row_hi) x cols [col_lo,col_hi)
+static torch::Tensor bn_bwd_apply_ragged(torch::Tensor go, torch::Tensor x,
+                                         torch::Tensor y, torch::Tensor mean,
+                                         torch::Tensor invstd, torch::Tensor w,
+                                         torch::Tensor gsum,
+                                         torch::Tensor gxsum, double n,
+                                         bool relu, bool region, int row_lo,
+                                         int row_hi, int col_lo, int col_hi) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous() &&
+              go.is_contiguous() && go.sizes() == x.sizes() &&
+              (!relu || (y.is_contiguous() && y.sizes() == x.sizes())));
+  const int64_t N = x.size(0), C = x.size(1), W = x.size(3);
+  const int64_t HW = x.size(2) * W;
+  const int64_t total = N * C * HW;
+  go = aligned16(go);
+  x = aligned16(x);
+  if (relu) y = aligned16(y);
+  auto gi = torch::empty_like(x);
+  const int vec = 16 / (int)x.element_size();
+  auto stream = at::cuda::getCurrentCUDAStream();
+  AT_DISPATCH_FLOATING_TYPES_AND2(
+      at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
+      "bn_bwd_apply_ragged", [&] {
+        auto launch = [&](auto kern) {
+          hipLaunchKernelGGL(
+              kern, dim3(grid_for((total + vec - 1) / vec, 256)), dim3(256), 0,
+              stream.stream(), go.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
+              relu ? y.data_ptr<scalar_t>() : (scalar_t*)nullptr,
+              gi.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+              invstd.data_ptr<float>(), w.data_ptr<float>(),
+              gsum.data_ptr<float>(), gxsum.data_ptr<float>(), 1.0 / n, total,
+              C, HW, (int)W, row_lo, row_hi, col_lo, col_hi);
+        };
+        if (region) {
+          if (relu) launch(bn_bwd_apply_ragged_kernel<scalar_t, true, true>);
+          else launch(bn_bwd_apply_ragged_kernel<scalar_t, false, true>);
+        } else {
+          if (relu) launch(bn_bwd_apply_ragged_kernel<scalar_t, true, false>);
+          else launch(bn_bwd_apply_ragged_kernel<scalar_t, false, false>);
+        }
+      });
+  return gi;
+}
+
 torch::Tensor bn_bwd_apply(torch::Tensor go, torch::Tensor x, torch::Tensor y,
                            torch::Tensor mean, torch::Tensor invstd,
                            torch::Tensor w, torch::Tensor gsum,
                            torch::Tensor gxsum, double n, bool relu) {
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  if (HW % 8 != 0)
+    return bn_bwd_apply_ragged(go, x, y, mean, invstd, w, gsum, gxsum, n, relu,
+                               false, 0, 0, 0, 0);
   auto gi = torch::empty_like(x);
   const int64_t total = N * C * HW;
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -1851,6 +2305,24 @@ torch::Tensor bn_bwd_apply(torch::Tensor go, torch::Tensor x, torch::Tensor y,
               gxsum.data_ptr<float>(), 1.0 / n, N, C, HW);
       });
   return gi;
+}
+
+// bn_bwd_apply when mean/var were taken over the region only
+// (margin = top, bottom, left, right); n counts region pixels.
+torch::Tensor bn_bwd_apply_region(torch::Tensor go, torch::Tensor x,
+                                  torch::Tensor y, torch::Tensor mean,
+                                  torch::Tensor invstd, torch::Tensor w,
+                                  torch::Tensor gsum, torch::Tensor gxsum,
+                                  double n, bool relu,
+                                  std::vector<int64_t> margin) {
+  TORCH_CHECK(x.dim() == 4);
+  const int64_t H = x.size(2), W = x.size(3);
+  check_margin(margin, H, W);
+  if (margin[0] + margin[1] + margin[2] + margin[3] == 0)
+    return bn_bwd_apply(go, x, y, mean, invstd, w, gsum, gxsum, n, relu);
+  return bn_bwd_apply_ragged(go, x, y, mean, invstd, w, gsum, gxsum, n, relu,
+                             true, (int)margin[0], (int)(H - margin[1]),
+                             (int)margin[2], (int)(W - margin[3]));
 }
 
 }  // namespace
@@ -1889,5 +2361,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("tracked"), pybind11::arg("mom"), pybind11::arg("n"),
         pybind11::arg("eps"), pybind11::arg("rezero") = false);
   m.def("bn_stats64_acc", &bn_stats64_acc);
+  m.def("bn_stats64_region_acc", &bn_stats64_region_acc, py::arg("x"),
+        py::arg("out"), py::arg("margin"));
+  m.def("bn_bwd_apply_region", &bn_bwd_apply_region, py::arg("go"),
+        py::arg("x"), py::arg("y"), py::arg("mean"), py::arg("invstd"),
+        py::arg("w"), py::arg("gsum"), py::arg("gxsum"), py::arg("n"),
+        py::arg("relu"), py::arg("margin"));
   m.attr("gfx_arch") = "gfx950";
 }

@@ -16,8 +16,12 @@ Our design keeps the same economics with exact semantics:
 * pools and stride-2 ops keep their D1 per-op exchange (pool divisor
   geometry under surplus is not worth the complexity — the reference's
   D2 pools silently change semantics instead);
-* the only train-mode deviation from D1 is BN statistics inside
-  conv_1x7_7x1 seeing surplus pixels (eval mode is exact).
+* BNs that run on a tensor still carrying surplus (after the leading
+  1x1 conv and after the 1x7) normalise every pixel but take their batch
+  statistics from the nominal tile only (TileBatchNorm2d.stat_margin),
+  so train mode computes the serial function too: forward, parameter
+  gradients and running statistics match the undistributed model
+  (tests/test_d2_exact.py).
 """
 
 from __future__ import annotations
@@ -53,14 +57,44 @@ def _op_halo_need(name: str) -> int:
     return 0
 
 
-def _make_op_d2(name, c, stride, ctx, mknorm):
-    """conv ops in d2 mode (outer pads only); everything else D1."""
+def _surplus(ctx, h):
+    """(top, bottom, left, right) surplus a halo-h fused exchange leaves
+    on THIS tile (HaloExchanger.pads_d2 semantics: interior sides get the
+    halo, image-boundary sides 0; a single tile has none)."""
+    if ctx is None or ctx["num_spatial_parts"] <= 1:
+        return (0, 0, 0, 0)
+    layout = TileLayout(ctx["num_spatial_parts"], ctx["slice_method"])
+    return HaloExchanger(
+        layout, ctx["spatial_local_rank"], ctx["rank_of_tile"]
+    ).pads_d2(h)
+
+
+def _bn_margin(bn, margin):
+    """BN (possibly wrapped by _bn_relu) whose batch statistics skip the
+    surplus ``margin`` of its input."""
+    if any(margin):
+        target = bn[0] if isinstance(bn, nn.Sequential) else bn
+        if not hasattr(target, "stat_margin"):
+            raise TypeError(
+                f"{type(target).__name__} cannot exclude a surplus margin "
+                "from its statistics; D2 spatial cells need TileBatchNorm2d"
+            )
+        target.stat_margin = tuple(margin)
+    return bn
+
+
+def _make_op_d2(name, c, stride, ctx, mknorm, ref_quirks=False):
+    """conv ops in d2 mode (outer pads only); everything else D1.
+
+    The BNs that run while the tensor still carries surplus pixels take
+    their statistics from the nominal tile only (stat_margin): the
+    surplus pixels are the neighbour's, which counts them itself."""
     if ctx is not None and stride == 1 and _op_halo_need(name):
         d2ctx = dict(ctx)
         if name == "conv_3x3":
             return nn.Sequential(
                 nn.Conv2d(c, c // 4, 1, bias=False),
-                _bn_relu(mknorm, c // 4),
+                _bn_margin(_bn_relu(mknorm, c // 4), _surplus(ctx, 1)),
                 nn.Identity(),
                 _d2conv(c // 4, c // 4, (3, 3), (1, 1), d2ctx),
                 _bn_relu(mknorm, c // 4),
@@ -68,13 +102,15 @@ def _make_op_d2(name, c, stride, ctx, mknorm):
                 nn.Conv2d(c // 4, c, 1, bias=False),
                 mknorm(c),
             )
-        # conv_1x7_7x1
+        # conv_1x7_7x1: the 1x7 consumes the column surplus, the 7x1 the
+        # row surplus
+        t, b, l, r = _surplus(ctx, 3)
         return nn.Sequential(
             nn.Conv2d(c, c // 4, 1, stride=1, bias=False),
-            _bn_relu(mknorm, c // 4),
+            _bn_margin(_bn_relu(mknorm, c // 4), (t, b, l, r)),
             nn.Identity(),
             _d2conv(c // 4, c // 4, (1, 7), (0, 3), d2ctx),
-            _bn_relu(mknorm, c // 4),
+            _bn_margin(_bn_relu(mknorm, c // 4), (t, b, 0, 0)),
             nn.Identity(),
             _d2conv(c // 4, c // 4, (7, 1), (3, 0), d2ctx),
             _bn_relu(mknorm, c // 4),
@@ -82,7 +118,7 @@ def _make_op_d2(name, c, stride, ctx, mknorm):
             nn.Conv2d(c // 4, c, 1, stride=1, bias=False),
             mknorm(c),
         )
-    return make_op(name, c, stride, ctx, mknorm)
+    return make_op(name, c, stride, ctx, mknorm, ref_quirks=ref_quirks)
 
 
 def _d2conv(cin, cout, k, pad, ctx):
@@ -112,6 +148,7 @@ class CellD2(nn.Module):
         reduction_prev,
         ctx=None,
         mknorm=nn.BatchNorm2d,
+        ref_quirks: bool = False,
     ):
         super().__init__()
         self.reduce1 = relu_conv_bn(channels_prev, channels, mknorm)
@@ -133,7 +170,10 @@ class CellD2(nn.Module):
         ]
         self.operations = nn.ModuleList()
         for (i, name), st in zip(ops, self.op_strides):
-            self.operations.append(_make_op_d2(name, channels, st, ctx, mknorm))
+            self.operations.append(
+                _make_op_d2(name, channels, st, ctx, mknorm,
+                            ref_quirks=ref_quirks)
+            )
 
         self.grad_mode = (ctx or {}).get("grad_mode", "exact")
         if ctx is not None and ctx["num_spatial_parts"] > 1:
@@ -208,8 +248,10 @@ def amoebanetd_d2(
     num_layers: int = 6,
     num_filters: int = 64,
     plan: Optional[SpatialPlan] = None,
+    ref_quirks: bool = False,
 ) -> nn.Sequential:
-    """D2 AmoebaNet-D; cell count/indices match amoebanet.amoebanetd."""
+    """D2 AmoebaNet-D; cell count/indices match amoebanet.amoebanetd
+    (``ref_quirks`` as there)."""
     assert num_layers % 3 == 0
     repeat = num_layers // 3
     channels = num_filters // 4
@@ -232,6 +274,7 @@ def amoebanetd_d2(
         cell = CellD2(
             state["c_pp"], state["c_p"], state["c"], reduction,
             state["red_prev"], ctx=ctx(), mknorm=mknorm(),
+            ref_quirks=ref_quirks,
         )
         state["c_pp"] = state["c_p"]
         state["c_p"] = state["c"] * len(cell.concat)

@@ -82,10 +82,16 @@ class BatchNormFn(torch.autograd.Function):
     the gsum/gxsum reduction terms are allreduced over the tile group,
     weight/bias grads stay LOCAL (the engine's spatial-group SUM
     allreduce aggregates them with the other parameter grads).
+
+    ``margin`` (top, bottom, left, right) != 0 says mean/invstd came from
+    the region inside the margin only (n_global counts region pixels):
+    the gsum/gxsum sums still run over every pixel, but their terms
+    reach region pixels only (bn_bwd_apply_region).
     """
 
     @staticmethod
-    def forward(ctx, x, weight, bias, mean, invstd, group, n_global, training, relu):
+    def forward(ctx, x, weight, bias, mean, invstd, group, n_global, training,
+                relu, margin=(0, 0, 0, 0)):
         ge = backend.ext()
         x = x.contiguous()
         w32 = weight.detach().float().contiguous()
@@ -97,6 +103,7 @@ class BatchNormFn(torch.autograd.Function):
         ctx.n_global = n_global
         ctx.training = training
         ctx.relu = relu
+        ctx.margin = tuple(margin) if training else (0, 0, 0, 0)
         return y
 
     @staticmethod
@@ -116,11 +123,18 @@ class BatchNormFn(torch.autograd.Function):
                 gf = g_global.float()
             else:
                 gf = sf
-            gi = ge.bn_bwd_apply(
-                go, x, y, mean, invstd, w32,
-                gf[:C].contiguous(), gf[C:].contiguous(),
-                float(ctx.n_global), ctx.relu,
-            )
+            if any(ctx.margin):
+                gi = ge.bn_bwd_apply_region(
+                    go, x, y, mean, invstd, w32,
+                    gf[:C].contiguous(), gf[C:].contiguous(),
+                    float(ctx.n_global), ctx.relu, list(ctx.margin),
+                )
+            else:
+                gi = ge.bn_bwd_apply(
+                    go, x, y, mean, invstd, w32,
+                    gf[:C].contiguous(), gf[C:].contiguous(),
+                    float(ctx.n_global), ctx.relu,
+                )
         else:
             # eval: mean/var are constants -> gi = go_eff * w * invstd
             zeros = torch.zeros(2 * C, device=x.device, dtype=torch.float32)
@@ -129,10 +143,11 @@ class BatchNormFn(torch.autograd.Function):
                 zeros[:C].contiguous(), zeros[C:].contiguous(),
                 1.0, ctx.relu,
             )
-        return (gi, gw.to(ctx.wdtype), gb.to(ctx.wdtype)) + (None,) * 6
+        return (gi, gw.to(ctx.wdtype), gb.to(ctx.wdtype)) + (None,) * 7
 
 
-def native_batchnorm(x, weight, bias, mean, invstd, group, n_global, training, relu=False):
+def native_batchnorm(x, weight, bias, mean, invstd, group, n_global, training,
+                     relu=False, margin=(0, 0, 0, 0)):
     return BatchNormFn.apply(
-        x, weight, bias, mean, invstd, group, n_global, training, relu
+        x, weight, bias, mean, invstd, group, n_global, training, relu, margin
     )

@@ -48,12 +48,22 @@ def allreduce_sum(t: torch.Tensor, group) -> torch.Tensor:
 
 
 class TileBatchNorm2d(nn.BatchNorm2d):
-    """Drop-in BatchNorm2d whose batch statistics span the tile group."""
+    """Drop-in BatchNorm2d whose batch statistics span the tile group.
 
-    def __init__(self, num_features: int, group=None, relu: bool = False, **kw):
+    ``stat_margin`` = (top, bottom, left, right): in training the batch
+    mean/variance, the count and the running-stat update use only the
+    region rows [top, H-bottom) x cols [left, W-right) of every plane,
+    while the normalisation applies to the whole tensor. A D2 surplus
+    tile sets it to its halo widths, so neighbour pixels (which the
+    neighbour counts itself) stay out of the statistics. Eval ignores
+    it; it is configuration, not state."""
+
+    def __init__(self, num_features: int, group=None, relu: bool = False,
+                 stat_margin=(0, 0, 0, 0), **kw):
         super().__init__(num_features, **kw)
         self.group = group
         self.relu = relu  # fused BN+ReLU (native GPU path only)
+        self.stat_margin = tuple(stat_margin)
 
     def _use_sync(self, x) -> bool:
         return (
@@ -63,26 +73,56 @@ class TileBatchNorm2d(nn.BatchNorm2d):
             and dist.is_initialized()
         )
 
+    def _margin(self, x):
+        """Active margin for this call (zero in eval); validates it."""
+        if not self.training:
+            return (0, 0, 0, 0)
+        mg = tuple(int(v) for v in self.stat_margin)
+        if len(mg) != 4 or min(mg) < 0:
+            raise ValueError(f"stat_margin must be 4 non-negative ints, got {mg}")
+        if any(mg) and (
+            mg[0] + mg[1] >= x.shape[-2] or mg[2] + mg[3] >= x.shape[-1]
+        ):
+            raise ValueError(
+                f"stat_margin {mg} leaves an empty region of a "
+                f"{x.shape[-2]}x{x.shape[-1]} plane"
+            )
+        return mg
+
     def forward(self, x):
+        mg = self._margin(x)
         if (
             x.is_cuda
             and not x.is_meta
-            and (x.shape[-2] * x.shape[-1]) % 8 == 0
             and os.environ.get("MPI4DL_NATIVE_BN", "1") != "0"
         ):
-            return self._forward_native(x)
-        if not self._use_sync(x):
+            return self._forward_native(x, mg)
+        if x.is_meta or not (self._use_sync(x) or any(mg)):
             y = super().forward(x)
             return torch.relu_(y) if self.relu else y
-        n_local = x.numel() // x.shape[1]
-        world = dist.get_world_size(group=self.group)
-        n = n_local * world  # tiles are equal-sized (power-of-two constraint)
+        t, b, l, r = mg
+        H, W = x.shape[-2], x.shape[-1]
+
+        def region(v):
+            return v[:, :, t : H - b, l : W - r] if any(mg) else v
+
+        n = region(x).numel() // x.shape[1]
+        group = self.group if self._use_sync(x) else None
+        if group is not None:
+            # tiles are equal-sized (power-of-two constraint)
+            n *= dist.get_world_size(group=group)
+
+        def total(v):
+            v = v.sum(dim=(0, 2, 3))
+            return allreduce_sum(v, group) if group is not None else v
+
         # two-pass variance: matches torch BN's centred formula closely
         # (the one-pass E[x^2]-mean^2 form loses ~1e-6 relative precision,
         # which measurably perturbs long BN chains)
-        mean = allreduce_sum(x.sum(dim=(0, 2, 3)), self.group) / n
+        mean = total(region(x)) / n
         centred = x - mean.view(1, -1, 1, 1)
-        var = allreduce_sum((centred * centred).sum(dim=(0, 2, 3)), self.group) / n
+        rc = region(centred)
+        var = total(rc * rc) / n
         if self.track_running_stats:
             with torch.no_grad():
                 m = self.momentum if self.momentum is not None else 0.1
@@ -98,14 +138,15 @@ class TileBatchNorm2d(nn.BatchNorm2d):
 
     # -- gemscore fused path (MI355X) ----------------------------------
 
-    def _forward_native(self, x):
+    def _forward_native(self, x, mg=(0, 0, 0, 0)):
         from . import backend
         from .native import native_batchnorm
 
         ge = backend.ext()
         x = x.contiguous()
         C = self.num_features
-        n = x.numel() // C
+        H, W = x.shape[-2], x.shape[-1]
+        n = x.shape[0] * (H - mg[0] - mg[1]) * (W - mg[2] - mg[3])
         group = self.group if (self.group is not None and dist.is_initialized()) else None
         if self.training:
             # persistent zeroed fp64 buffer: stats64 accumulates into it
@@ -116,7 +157,10 @@ class TileBatchNorm2d(nn.BatchNorm2d):
             if buf is None or buf.device != x.device or buf.numel() != 2 * C:
                 buf = torch.zeros(2 * C, device=x.device, dtype=torch.float64)
                 self._stats64 = buf
-            stats = ge.bn_stats64_acc(x, buf)
+            if any(mg) or (H * W) % 8:
+                stats = ge.bn_stats64_region_acc(x, buf, list(mg))
+            else:
+                stats = ge.bn_stats64_acc(x, buf)
             if group is not None:
                 dist.all_reduce(stats, group=group)
                 n *= dist.get_world_size(group=group)
@@ -134,5 +178,5 @@ class TileBatchNorm2d(nn.BatchNorm2d):
             invstd = torch.rsqrt(self.running_var.float() + self.eps).contiguous()
         return native_batchnorm(
             x, self.weight, self.bias, mean.contiguous(), invstd.contiguous(),
-            group, float(n), self.training, self.relu,
+            group, float(n), self.training, self.relu, mg,
         )

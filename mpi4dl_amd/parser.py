@@ -47,7 +47,9 @@ def get_parser() -> argparse.ArgumentParser:
                    help="csv: cells per partition")
     p.add_argument("--halo-d2", "--halo-D2", action="store_true",
                    dest="halo_d2",
-                   help="use the D2 fused-halo model variant "
+                   help="use the D2 fused-halo model variant of the "
+                        "resnet and amoebanet families: one halo exchange "
+                        "feeds several convs, training stays exact "
                         "(--halo-D2 = the reference's spelling)")
     p.add_argument("--fused-layers", type=int, default=4,
                    help="blocks per fused D2 halo exchange")
