@@ -255,7 +255,10 @@ __global__ __launch_bounds__(256) void conv_fwd_v2_kernel(
   // are issued while tile t computes; the LDS write of tile t+1 sits
   // right after the single per-iteration barrier, so its vmcnt wait is
   // hidden under the previous iteration's MFMAs.
-  const int S = SS > 0 ? SS : g.S;
+  static_assert(SS == 1 || SS == 3 || SS == 7,
+                "v2 stages exactly SS shifted copies of a 16/24-element "
+                "row segment: other kernel widths run conv_fwd_kernel");
+  constexpr int S = SS;
   constexpr int UNITS = (SS == 1) ? 2 : 1;  // S==1: 32 c's -> 512 units
   constexpr int BMV = 32 * MFRAG;
   constexpr int ACH = BMV * 4;              // A chunks (8 shorts each)
@@ -410,7 +413,7 @@ __global__ __launch_bounds__(256) void conv_fwd_v2_kernel(
             break;
         }
 #pragma unroll
-        for (int ss = 0; ss < (SS > 0 ? SS : 1); ++ss) {
+        for (int ss = 0; ss < SS; ++ss) {
           const int kk = c * S + ss - kk0;
           if (kk < 0 || kk >= BK) continue;
           short v[8];
@@ -683,8 +686,13 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor w,
   }
   auto stream = at::cuda::getCurrentCUDAStream();
   const int64_t OHW = (int64_t)g.OH * g.OW;
-  if (g.sh == 1 && g.sw == 1 && g.C * g.S >= BK && OHW % BN == 0 &&
-      g.OW % 8 == 0) {
+  // v2 exists for S in {1, 3, 7} only: its fast path keeps a 16- or
+  // 24-element row segment in registers and writes SS compile-time
+  // shifted copies of it. Every other kernel width runs the fully
+  // guarded v1 kernel below.
+  const bool v2_width = (g.S == 1 || g.S == 3 || g.S == 7);
+  if (g.sh == 1 && g.sw == 1 && v2_width && g.C * g.S >= BK &&
+      OHW % BN == 0 && g.OW % 8 == 0) {
     // v2: row-pass kernel with [K][R][C*S]-permuted weights; global
     // pixel axis + M-adaptive BM (32/64/128 by K)
     auto w2 = w.view({g.K, g.C, g.R, g.S})
@@ -712,9 +720,7 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor w,
       case 12: launch_v2(conv_fwd_v2_kernel<1, 2>); break;
       case 14: launch_v2(conv_fwd_v2_kernel<1, 4>); break;
       default:
-        if (mfrag == 1) launch_v2(conv_fwd_v2_kernel<0, 1>);
-        else if (mfrag == 2) launch_v2(conv_fwd_v2_kernel<0, 2>);
-        else launch_v2(conv_fwd_v2_kernel<0, 4>);
+        TORCH_CHECK(false, "conv_fwd: no v2 kernel for S=", g.S);
     }
     return out;
   }
