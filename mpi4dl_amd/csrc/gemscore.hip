@@ -1094,245 +1094,37 @@ avgpool3s1_bwd_vec(const T* __restrict__ go, T* __restrict__ gi, int64_t NC,
 }
 
 // ---------------------------------------------------------------------------
-// Fused BatchNorm (NCHW): fp64-accumulated channel stats, one
-// normalize+affine(+ReLU) pass, gather-formulated backward.
-// Replaces MIOpenBatchNorm{Fwd,Bwd}Spatial (14.3% of step time) and the
-// surrounding unfused elementwise casts; doubles as the local-stats leg
-// of TileBatchNorm2d's cross-tile sync (python does one allreduce of the
-// [sum,sumsq] / [gsum,gxsum] vectors between the two kernels).
-// ---------------------------------------------------------------------------
-
-typedef __attribute__((ext_vector_type(8))) short short8v;
-
-template <typename T>
-__device__ __forceinline__ float to_f32(T v) { return (float)v; }
-
-// 2D grid: x = channel, y = HW chunk (the chip needs >>256 workgroups —
-// guide G1/G11); 16-byte vector loads (G13); fp64 accumulation with one
-// fp64 atomicAdd per block per output.
-template <typename T>
-__global__ void bn_stats64_kernel(const T* __restrict__ x,
-                                  double* __restrict__ out, int64_t N,
-                                  int64_t C, int64_t HW, int64_t chunk) {
-  const int64_t ch = blockIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.y * chunk;
-  const int64_t i1 = min(i0 + chunk, HW);
-  double s = 0.0, ss = 0.0;
-  const int VEC = sizeof(T) == 2 ? 8 : 4;
-  for (int64_t n = 0; n < N; ++n) {
-    const T* p = x + (n * C + ch) * HW;
-    int64_t i = i0 + (int64_t)threadIdx.x * VEC;
-    if (sizeof(T) == 2) {
-      for (; i + 8 <= i1; i += (int64_t)blockDim.x * 8) {
-        short8v v = *(const short8v*)(p + i);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float f = to_f32(((const T*)&v)[e]);
-          s += (double)f;
-          ss += (double)(f * f);
-        }
-      }
-    } else {
-      for (; i + 4 <= i1; i += (int64_t)blockDim.x * 4) {
-        const float4 v = *(const float4*)((const float*)p + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float f = ((const float*)&v)[e];
-          s += (double)f;
-          ss += (double)(f * f);
-        }
-      }
-    }
-    // tail (only the last chunk can be ragged)
-    if (blockIdx.y == gridDim.y - 1) {
-      int64_t tail0 = i1 - (i1 % VEC);
-      for (int64_t t = tail0 + threadIdx.x; t < i1; t += blockDim.x) {
-        const float f = to_f32(p[t]);
-        s += (double)f;
-        ss += (double)(f * f);
-      }
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    s += __shfl_down(s, off, 64);
-    ss += __shfl_down(ss, off, 64);
-  }
-  __shared__ double ls[8], lss[8];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { ls[wid] = s; lss[wid] = ss; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double ts = 0.0, tss = 0.0;
-    for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) { ts += ls[wv]; tss += lss[wv]; }
-    atomicAdd(&out[ch], ts);
-    atomicAdd(&out[C + ch], tss);
-  }
-}
-
-template <typename T, bool RELU>
-__global__ void bn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
-                                const float* __restrict__ mean,
-                                const float* __restrict__ invstd,
-                                const float* __restrict__ wgt,
-                                const float* __restrict__ bias, int64_t N,
-                                int64_t C, int64_t HW) {
-  // 8 elements per thread (HW % 8 == 0 fast path enforced host-side)
-  const int64_t total8 = N * C * HW / 8;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i8 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i8 < total8; i8 += stride) {
-    const int64_t i = i8 * 8;
-    const int64_t ch = (i / HW) % C;
-    const float m = mean[ch], inv = invstd[ch], w = wgt[ch], b = bias[ch];
-    if (sizeof(T) == 2) {
-      short8v vx = *(const short8v*)((const short*)x + i);
-      short8v vy;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = (to_f32(((const T*)&vx)[e]) - m) * inv * w + b;
-        if (RELU) v = v > 0.f ? v : 0.f;
-        ((T*)&vy)[e] = (T)v;
-      }
-      *(short8v*)((short*)y + i) = vy;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = ((float)x[i + e] - m) * inv * w + b;
-        if (RELU) v = v > 0.f ? v : 0.f;
-        y[i + e] = (T)v;
-      }
-    }
-  }
-}
-
-// per-channel [gsum, gxsum] where gxsum = sum(go * xhat); RELU masks go
-// by (y > 0) — pass y=nullptr when no fusion. 2D grid + vector loads.
-template <typename T, bool RELU>
-__global__ void bn_bwd_stats_kernel(const T* __restrict__ go,
-                                    const T* __restrict__ x,
-                                    const T* __restrict__ y,
-                                    const float* __restrict__ mean,
-                                    const float* __restrict__ invstd,
-                                    double* __restrict__ out, int64_t N,
-                                    int64_t C, int64_t HW, int64_t chunk) {
-  const int64_t ch = blockIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.y * chunk;
-  const int64_t i1 = min(i0 + chunk, HW);
-  const float m = mean[ch], inv = invstd[ch];
-  double gs = 0.0, gx = 0.0;
-  for (int64_t n = 0; n < N; ++n) {
-    const int64_t off = (n * C + ch) * HW;
-    if (sizeof(T) == 2) {
-      int64_t i = i0 + (int64_t)threadIdx.x * 8;
-      for (; i + 8 <= i1; i += (int64_t)blockDim.x * 8) {
-        short8v vg = *(const short8v*)((const short*)go + off + i);
-        short8v vx = *(const short8v*)((const short*)x + off + i);
-        short8v vy;
-        if (RELU) vy = *(const short8v*)((const short*)y + off + i);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float g = to_f32(((const T*)&vg)[e]);
-          if (RELU && to_f32(((const T*)&vy)[e]) <= 0.f) g = 0.f;
-          const float xh = (to_f32(((const T*)&vx)[e]) - m) * inv;
-          gs += (double)g;
-          gx += (double)(g * xh);
-        }
-      }
-      if (blockIdx.y == gridDim.y - 1) {
-        int64_t tail0 = i1 - (i1 % 8);
-        for (int64_t t = tail0 + threadIdx.x; t < i1; t += blockDim.x) {
-          float g = (float)go[off + t];
-          if (RELU && (float)y[off + t] <= 0.f) g = 0.f;
-          const float xh = ((float)x[off + t] - m) * inv;
-          gs += (double)g;
-          gx += (double)(g * xh);
-        }
-      }
-    } else {
-      for (int64_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-        float g = (float)go[off + i];
-        if (RELU && (float)y[off + i] <= 0.f) g = 0.f;
-        const float xh = ((float)x[off + i] - m) * inv;
-        gs += (double)g;
-        gx += (double)(g * xh);
-      }
-    }
-  }
-  for (int off2 = 32; off2 > 0; off2 >>= 1) {
-    gs += __shfl_down(gs, off2, 64);
-    gx += __shfl_down(gx, off2, 64);
-  }
-  __shared__ double l1[8], l2[8];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { l1[wid] = gs; l2[wid] = gx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t1 = 0.0, t2 = 0.0;
-    for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) { t1 += l1[wv]; t2 += l2[wv]; }
-    atomicAdd(&out[ch], t1);
-    atomicAdd(&out[C + ch], t2);
-  }
-}
-
-template <typename T, bool RELU>
-__global__ void bn_bwd_apply_kernel(const T* __restrict__ go,
-                                    const T* __restrict__ x,
-                                    const T* __restrict__ y,
-                                    T* __restrict__ gi,
-                                    const float* __restrict__ mean,
-                                    const float* __restrict__ invstd,
-                                    const float* __restrict__ wgt,
-                                    const float* __restrict__ gsum,
-                                    const float* __restrict__ gxsum,
-                                    double inv_n, int64_t N, int64_t C,
-                                    int64_t HW) {
-  const int64_t total8 = N * C * HW / 8;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i8 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i8 < total8; i8 += stride) {
-    const int64_t i = i8 * 8;
-    const int64_t ch = (i / HW) % C;
-    const float m = mean[ch], inv = invstd[ch], w = wgt[ch];
-    const float gsn = (float)(gsum[ch] * inv_n);
-    const float gxn = (float)(gxsum[ch] * inv_n);
-    if (sizeof(T) == 2) {
-      short8v vg = *(const short8v*)((const short*)go + i);
-      short8v vx = *(const short8v*)((const short*)x + i);
-      short8v vy;
-      if (RELU) vy = *(const short8v*)((const short*)y + i);
-      short8v vo;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float g = to_f32(((const T*)&vg)[e]);
-        if (RELU && to_f32(((const T*)&vy)[e]) <= 0.f) g = 0.f;
-        const float xh = (to_f32(((const T*)&vx)[e]) - m) * inv;
-        ((T*)&vo)[e] = (T)((g - gsn - xh * gxn) * w * inv);
-      }
-      *(short8v*)((short*)gi + i) = vo;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float g = (float)go[i + e];
-        if (RELU && (float)y[i + e] <= 0.f) g = 0.f;
-        const float xh = ((float)x[i + e] - m) * inv;
-        gi[i + e] = (T)((g - gsn - xh * gxn) * w * inv);
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Ragged / region BatchNorm kernels: any H, W (surplus tiles of the D2
-// fused-halo design are e.g. 259x259) and statistics restricted to a
-// region = rows [top, H-bottom) x cols [left, W-right) of every plane.
+// Fused BatchNorm (NCHW), one kernel family for every plane shape:
+// fp64-accumulated channel stats, one normalize+affine(+ReLU) pass,
+// gather-formulated backward. Replaces MIOpenBatchNorm{Fwd,Bwd}Spatial
+// and the surrounding unfused elementwise casts; doubles as the
+// local-stats leg of TileBatchNorm2d's cross-tile sync (python does one
+// allreduce of the [sum,sumsq] / [gsum,gxsum] vectors between the two
+// kernels). Statistics may be restricted to a region = rows
+// [top, H-bottom) x cols [left, W-right) of every plane (surplus tiles
+// of the D2 fused-halo design are e.g. 259x259 with a margin).
 //
-// All of them walk 16-byte SLOTS of the flat tensor (the tensor base is
+// All kernels walk 16-byte SLOTS of the flat tensor (the tensor base is
 // 16-byte aligned — enforced host-side), so every vector access is
 // aligned whatever the row / plane start is. The reductions load a whole
 // slot wherever it lies inside the tensor and mask the elements outside
 // their range (head and tail of a row or plane); the elementwise kernels
-// resolve a slot that straddles a plane seam per element.
+// resolve a slot that straddles a plane seam per element. Both give every
+// element the same arithmetic whichever way its slot was resolved, so
+// results do not depend on where the planes fall on the slot grid.
+//
+// WHOLE (apply, backward statistics, backward apply): the host saw that
+// every access is a whole in-bounds slot — HW is a multiple of VEC — so
+// the element masks, the bounds test and the per-element branch compile
+// out; the body is otherwise the same. Measured on the benchmark
+// (profiles/PERF_NOTES.md): without it these kernels are up to 4 % slower
+// on whole-slot planes than the aligned kernels they replaced. The
+// full-plane statistics stayed slower even so, and keep their aligned
+// kernel (bn_stats64_kernel) on the same predicate.
 // ---------------------------------------------------------------------------
+
+template <typename T>
+__device__ __forceinline__ float to_f32(T v) { return (float)v; }
 
 // [sum, sumsq] of the elements of slot [v0, v0+VEC) that lie in [a, e).
 template <typename T>
@@ -1387,10 +1179,11 @@ __device__ __forceinline__ uint32_t fast_div(uint32_t j, uint32_t d,
   return d == 1 ? j : __umulhi(j, m);
 }
 
-// Contiguous range [start, start+total) of every plane (a region whose
-// rows are full width). 2D grid: x = channel, y = chunk; the chunk
-// windows start at the plane range's first SLOT, so every block walks
-// chunk/VEC whole slots whatever the plane's alignment.
+// Contiguous range [start, start+total) of every plane: the whole plane,
+// or a region whose rows are full width. 2D grid: x = channel, y = chunk
+// (the chip needs >>256 workgroups); the chunk windows start at the plane
+// range's first SLOT, so every block walks chunk/VEC whole slots whatever
+// the plane's alignment.
 template <typename T>
 __global__ void bn_stats64_span_kernel(const T* __restrict__ x,
                                        double* __restrict__ out, int64_t N,
@@ -1408,6 +1201,36 @@ __global__ void bn_stats64_span_kernel(const T* __restrict__ x,
     for (int64_t v0 = w0 + (int64_t)threadIdx.x * VEC; v0 < e;
          v0 += (int64_t)blockDim.x * VEC)
       stats_slot<T>(x, v0, a, e, numel, s, ss);
+  }
+  stats_block_commit(s, ss, out, C, ch);
+}
+
+// The whole plane when every plane is made of whole slots (HW % VEC == 0,
+// aligned base): chunk windows are plain element ranges of the plane and
+// nothing is masked. Kept beside the span kernel because the span kernel,
+// even with its masks compiled out, measured 1.1-1.7 % slower on the
+// benchmark's planes (profiles/PERF_NOTES.md).
+template <typename T>
+__global__ void bn_stats64_kernel(const T* __restrict__ x,
+                                  double* __restrict__ out, int64_t N,
+                                  int64_t C, int64_t HW, int64_t chunk) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int64_t ch = blockIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.y * chunk;
+  const int64_t i1 = min(i0 + chunk, HW);
+  double s = 0.0, ss = 0.0;
+  for (int64_t n = 0; n < N; ++n) {
+    const T* p = x + (n * C + ch) * HW;
+    for (int64_t i = i0 + (int64_t)threadIdx.x * VEC; i + VEC <= i1;
+         i += (int64_t)blockDim.x * VEC) {
+      const uint4 raw = *(const uint4*)(p + i);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const float f = to_f32(((const T*)&raw)[k]);
+        s += (double)f;
+        ss += (double)(f * f);
+      }
+    }
   }
   stats_block_commit(s, ss, out, C, ch);
 }
@@ -1444,16 +1267,16 @@ __global__ void bn_stats64_region_kernel(const T* __restrict__ x,
   stats_block_commit(s, ss, out, C, ch);
 }
 
-// bn_apply_kernel for any HW: a slot inside one plane takes its channel
-// once; a slot across a plane seam or the flat tail goes per element.
-template <typename T, bool RELU>
-__global__ void bn_apply_ragged_kernel(const T* __restrict__ x,
-                                       T* __restrict__ y,
-                                       const float* __restrict__ mean,
-                                       const float* __restrict__ invstd,
-                                       const float* __restrict__ wgt,
-                                       const float* __restrict__ bias,
-                                       int64_t total, int64_t C, int64_t HW) {
+// y = (x - mean) * invstd * w + b (+ ReLU). A slot inside one plane takes
+// its channel once; a slot across a plane seam or the flat tail goes per
+// element.
+template <typename T, bool RELU, bool WHOLE>
+__global__ void bn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
+                                const float* __restrict__ mean,
+                                const float* __restrict__ invstd,
+                                const float* __restrict__ wgt,
+                                const float* __restrict__ bias, int64_t total,
+                                int64_t C, int64_t HW) {
   constexpr int VEC = 16 / sizeof(T);
   const int64_t nvec = (total + VEC - 1) / VEC;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -1461,7 +1284,7 @@ __global__ void bn_apply_ragged_kernel(const T* __restrict__ x,
        iv += stride) {
     const int64_t i = iv * VEC;
     const int64_t p0 = i / HW;
-    if (i + VEC <= total && i - p0 * HW + VEC <= HW) {
+    if (WHOLE || (i + VEC <= total && i - p0 * HW + VEC <= HW)) {
       const int64_t ch = p0 % C;
       const float m = mean[ch], inv = invstd[ch], w = wgt[ch], b = bias[ch];
       const uint4 rx = *(const uint4*)(x + i);
@@ -1485,18 +1308,18 @@ __global__ void bn_apply_ragged_kernel(const T* __restrict__ x,
   }
 }
 
-// bn_bwd_stats_kernel for any HW: block (ch, y) sums one chunk of every
-// image's plane; chunk windows start at the plane's first slot (see
-// bn_stats64_span_kernel), elements outside the plane are masked.
-template <typename T, bool RELU>
-__global__ void bn_bwd_stats_ragged_kernel(const T* __restrict__ go,
-                                           const T* __restrict__ x,
-                                           const T* __restrict__ y,
-                                           const float* __restrict__ mean,
-                                           const float* __restrict__ invstd,
-                                           double* __restrict__ out, int64_t N,
-                                           int64_t C, int64_t HW,
-                                           int64_t chunk) {
+// per-channel [gsum, gxsum] where gxsum = sum(go * xhat); RELU masks go
+// by (y > 0) — pass y=nullptr when no fusion. Block (ch, y) sums one chunk
+// of every image's plane; chunk windows start at the plane's first slot
+// (see bn_stats64_span_kernel), elements outside the plane are masked.
+template <typename T, bool RELU, bool WHOLE>
+__global__ void bn_bwd_stats_kernel(const T* __restrict__ go,
+                                    const T* __restrict__ x,
+                                    const T* __restrict__ y,
+                                    const float* __restrict__ mean,
+                                    const float* __restrict__ invstd,
+                                    double* __restrict__ out, int64_t N,
+                                    int64_t C, int64_t HW, int64_t chunk) {
   constexpr int VEC = 16 / sizeof(T);
   const int64_t ch = blockIdx.x;
   const int64_t numel = N * C * HW;
@@ -1509,9 +1332,9 @@ __global__ void bn_bwd_stats_ragged_kernel(const T* __restrict__ go,
     const int64_t e = min(a0 + HW, w0 + chunk);
     for (int64_t v0 = w0 + (int64_t)threadIdx.x * VEC; v0 < e;
          v0 += (int64_t)blockDim.x * VEC) {
-      const int lo = (int)max(a - v0, (int64_t)0);
-      const int hi = (int)min(e - v0, (int64_t)VEC);
-      if (v0 + VEC <= numel) {
+      const int lo = WHOLE ? 0 : (int)max(a - v0, (int64_t)0);
+      const int hi = WHOLE ? VEC : (int)min(e - v0, (int64_t)VEC);
+      if (WHOLE || v0 + VEC <= numel) {
         const uint4 rg = *(const uint4*)(go + v0);
         const uint4 rx = *(const uint4*)(x + v0);
         uint4 ry;
@@ -1539,12 +1362,19 @@ __global__ void bn_bwd_stats_ragged_kernel(const T* __restrict__ go,
   stats_block_commit(gs, gx, out, C, ch);
 }
 
-// bn_bwd_apply_kernel for any HW. REGION: mean/var came from the region
-// pixels only while every pixel was normalised, so the two reduction
-// terms reach region pixels only:
+// gi of one element; `reduced` = the two reduction terms reach this pixel
+__device__ __forceinline__ float bn_bwd_elem(float g, float xh, float gsn,
+                                             float gxn, float w, float inv,
+                                             bool reduced) {
+  return (reduced ? g - gsn - xh * gxn : g) * w * inv;
+}
+
+// gi = w*inv*(g - gsum/n - xhat*gxsum/n). REGION: mean/var came from the
+// region pixels only while every pixel was normalised, so the two
+// reduction terms reach region pixels only:
 //   gi_p = w*inv*[g_p - 1{p in region}*(gsum/n + xhat_p*gxsum/n)]
-template <typename T, bool RELU, bool REGION>
-__global__ void bn_bwd_apply_ragged_kernel(
+template <typename T, bool RELU, bool REGION, bool WHOLE>
+__global__ void bn_bwd_apply_kernel(
     const T* __restrict__ go, const T* __restrict__ x, const T* __restrict__ y,
     T* __restrict__ gi, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ wgt,
@@ -1559,7 +1389,7 @@ __global__ void bn_bwd_apply_ragged_kernel(
     const int64_t i = iv * VEC;
     const int64_t p0 = i / HW;
     const int64_t rem = i - p0 * HW;
-    if (i + VEC <= total && rem + VEC <= HW) {
+    if (WHOLE || (i + VEC <= total && rem + VEC <= HW)) {
       const int64_t ch = p0 % C;
       const float m = mean[ch], inv = invstd[ch], w = wgt[ch];
       const float gsn = (float)(gsum[ch] * inv_n);
@@ -1579,13 +1409,13 @@ __global__ void bn_bwd_apply_ragged_kernel(
         float g = to_f32(((const T*)&rg)[e]);
         if (RELU && to_f32(((const T*)&ry)[e]) <= 0.f) g = 0.f;
         const float xh = (to_f32(((const T*)&rx)[e]) - m) * inv;
-        float red = gsn + xh * gxn;
+        bool reduced = true;
         if (REGION) {
-          if (row < row_lo || row >= row_hi || col < col_lo || col >= col_hi)
-            red = 0.f;
+          reduced = row >= row_lo && row < row_hi && col >= col_lo &&
+                    col < col_hi;
           if (++col == W) { col = 0; ++row; }
         }
-        ((T*)&ro)[e] = (T)((g - red) * w * inv);
+        ((T*)&ro)[e] = (T)bn_bwd_elem(g, xh, gsn, gxn, w, inv, reduced);
       }
       *(uint4*)(gi + i) = ro;
     } else {
@@ -1597,15 +1427,17 @@ __global__ void bn_bwd_apply_ragged_kernel(
         float g = to_f32(go[k]);
         if (RELU && to_f32(y[k]) <= 0.f) g = 0.f;
         const float xh = (to_f32(x[k]) - mean[ch]) * inv;
-        float red = (float)(gsum[ch] * inv_n) + xh * (float)(gxsum[ch] * inv_n);
+        bool reduced = true;
         if (REGION) {
           const int64_t q = k - p * HW;
           const int row = (int)(q / W);
           const int col = (int)(q - (int64_t)row * W);
-          if (row < row_lo || row >= row_hi || col < col_lo || col >= col_hi)
-            red = 0.f;
+          reduced = row >= row_lo && row < row_hi && col >= col_lo &&
+                    col < col_hi;
         }
-        gi[k] = (T)((g - red) * wgt[ch] * inv);
+        gi[k] = (T)bn_bwd_elem(g, xh, (float)(gsum[ch] * inv_n),
+                               (float)(gxsum[ch] * inv_n), wgt[ch], inv,
+                               reduced);
       }
     }
   }
@@ -1999,60 +1831,34 @@ torch::Tensor avgpool_bwd(torch::Tensor go, int64_t H, int64_t W, int64_t k,
   return gi;
 }
 
-static int64_t stats_splits(int64_t C, int64_t HW) {
-  // target ~2048 workgroups (256 CUs x 8); chunk in multiples of 2048
-  int64_t splits = std::max<int64_t>(1, 2048 / std::max<int64_t>(C, 1));
-  int64_t max_splits = std::max<int64_t>(1, (HW + 2047) / 2048);
-  return std::min(splits, max_splits);
+// ---------------- BatchNorm bindings ----------------
+// Every binding checks its arguments first, for every shape: x is a
+// contiguous 4-D CUDA tensor, go / y are laid out like x, the per-channel
+// vectors are fp32 of length C. A base off the 16-byte grid is cloned.
+
+static void check_bn_x(const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous(),
+              "bn: x must be a contiguous 4-D CUDA tensor");
 }
 
-torch::Tensor bn_stats64(torch::Tensor x) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
-  const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
-  auto out = torch::zeros({2 * C}, x.options().dtype(torch::kDouble));
-  const int64_t splits = stats_splits(C, HW);
-  int64_t chunk = (HW + splits - 1) / splits;
-  chunk = ((chunk + 2047) / 2048) * 2048;
-  const int64_t gy = (HW + chunk - 1) / chunk;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  AT_DISPATCH_FLOATING_TYPES_AND2(
-      at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
-      "bn_stats64", [&] {
-        hipLaunchKernelGGL((bn_stats64_kernel<scalar_t>),
-                           dim3((uint32_t)C, (uint32_t)gy), dim3(256), 0,
-                           stream.stream(), x.data_ptr<scalar_t>(),
-                           out.data_ptr<double>(), N, C, HW, chunk);
-      });
-  return out;
+static void check_bn_like(const torch::Tensor& t, const torch::Tensor& x,
+                          const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.sizes() == x.sizes() &&
+                  t.scalar_type() == x.scalar_type(),
+              "bn: ", name, " must be contiguous with x's shape and dtype");
 }
 
-// accumulate into a caller-owned ZEROED fp64 buffer (persistent across
-// steps; bn_finalize(..., rezero=true) restores the invariant) — kills
-// the per-BN-call torch.zeros fill kernel (~3k launches/step).
-torch::Tensor bn_stats64_acc(torch::Tensor x, torch::Tensor out) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
-  const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+static void check_bn_vec(const torch::Tensor& v, int64_t C, const char* name) {
+  TORCH_CHECK(v.is_cuda() && v.scalar_type() == torch::kFloat &&
+                  v.is_contiguous() && v.numel() == C,
+              "bn: ", name, " must be a contiguous fp32 CUDA vector of ", C,
+              " channels");
+}
+
+static void check_bn_out(const torch::Tensor& out, int64_t C) {
   TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
-              out.scalar_type() == torch::kDouble && out.numel() == 2 * C);
-  const int64_t splits = stats_splits(C, HW);
-  int64_t chunk = (HW + splits - 1) / splits;
-  chunk = ((chunk + 2047) / 2048) * 2048;
-  const int64_t gy = (HW + chunk - 1) / chunk;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  AT_DISPATCH_FLOATING_TYPES_AND2(
-      at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
-      "bn_stats64_acc", [&] {
-        hipLaunchKernelGGL((bn_stats64_kernel<scalar_t>),
-                           dim3((uint32_t)C, (uint32_t)gy), dim3(256), 0,
-                           stream.stream(), x.data_ptr<scalar_t>(),
-                           out.data_ptr<double>(), N, C, HW, chunk);
-      });
-  return out;
-}
-
-// the ragged kernels take 16-byte slots of the flat tensor from its base
-static torch::Tensor aligned16(const torch::Tensor& t) {
-  return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) ? t.clone() : t;
+                  out.scalar_type() == torch::kDouble && out.numel() == 2 * C,
+              "bn: out must be a contiguous fp64 CUDA vector of 2*C");
 }
 
 static void check_margin(const std::vector<int64_t>& mg, int64_t H,
@@ -2063,42 +1869,82 @@ static void check_margin(const std::vector<int64_t>& mg, int64_t H,
               "margin leaves an empty region of a ", H, "x", W, " plane");
 }
 
-// bn_stats64_acc over the region only (margin = top, bottom, left, right).
+// the BN kernels take 16-byte slots of the flat tensor from its base
+static torch::Tensor slot_aligned(const torch::Tensor& t) {
+  return aligned16(t.data_ptr()) ? t : t.clone();
+}
+
+// f(std::true_type / std::false_type) for a run-time bool: one launch site
+// serves every instantiation of a kernel's bool template parameters
+template <typename F>
+static void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// (chunk, gy) of a stats grid that sums `span` elements of every plane:
+// ~2048 workgroups (256 CUs x 8) over C channels, chunk a multiple of
+// 2048. A chunk window starts at the first slot of the plane's range, up
+// to `slack` elements before the range itself.
+static std::pair<int64_t, int64_t> stats_grid(int64_t C, int64_t HW,
+                                              int64_t span, int64_t slack) {
+  const int64_t splits =
+      std::min(std::max<int64_t>(1, 2048 / std::max<int64_t>(C, 1)),
+               std::max<int64_t>(1, (HW + 2047) / 2048));
+  const int64_t chunk = ((HW + splits - 1) / splits + 2047) / 2048 * 2048;
+  return {chunk, (span + slack + chunk - 1) / chunk};
+}
+
+// slack of a range that starts `start` into every plane of an aligned
+// tensor: none when all of them start on a slot boundary
+static int64_t slot_slack(int64_t vec, int64_t HW, int64_t start) {
+  return (HW % vec == 0 && start % vec == 0) ? 0 : vec - 1;
+}
+
+// WHOLE of the kernels: every plane of an aligned tensor is made of whole
+// in-bounds slots
+static bool planes_whole(int64_t vec, int64_t HW) { return HW % vec == 0; }
+
+// Accumulate [sum, sumsq] of the region (margin = top, bottom, left,
+// right) into a caller-owned ZEROED fp64 buffer (persistent across steps;
+// bn_finalize(..., rezero=true) restores the invariant) — kills the
+// per-BN-call torch.zeros fill kernel (~3k launches/step).
 torch::Tensor bn_stats64_region_acc(torch::Tensor x, torch::Tensor out,
                                     std::vector<int64_t> margin) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
+  check_bn_x(x);
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int64_t HW = H * W;
   check_margin(margin, H, W);
+  check_bn_out(out, C);
   const int64_t mt = margin[0], mb = margin[1], ml = margin[2], mr = margin[3];
-  if (mt + mb + ml + mr == 0 && HW % 8 == 0) return bn_stats64_acc(x, out);
-  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
-              out.scalar_type() == torch::kDouble && out.numel() == 2 * C);
-  TORCH_CHECK(HW < (int64_t)1 << 30, "plane too large");
-  x = aligned16(x);
-  const int64_t splits = stats_splits(C, HW);
-  int64_t chunk = (HW + splits - 1) / splits;
-  chunk = ((chunk + 2047) / 2048) * 2048;
+  x = slot_aligned(x);
   const int64_t Hr = H - mt - mb;
-  const int vec = 16 / (int)x.element_size();
+  const int64_t vec = 16 / (int64_t)x.element_size();
   auto stream = at::cuda::getCurrentCUDAStream();
   if (ml + mr == 0) {
     // full-width rows: one contiguous range per plane
     const int64_t start = mt * W, total = Hr * W;
-    const int64_t gy = (total + vec - 1 + chunk - 1) / chunk;
+    const auto cg = stats_grid(C, HW, total, slot_slack(vec, HW, start));
+    const int64_t chunk = cg.first, gy = cg.second;
     AT_DISPATCH_FLOATING_TYPES_AND2(
         at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
         "bn_stats64_span", [&] {
-          hipLaunchKernelGGL((bn_stats64_span_kernel<scalar_t>),
-                             dim3((uint32_t)C, (uint32_t)gy), dim3(256), 0,
-                             stream.stream(), x.data_ptr<scalar_t>(),
-                             out.data_ptr<double>(), N, C, HW, start, total,
-                             chunk);
+          const dim3 grid((uint32_t)C, (uint32_t)gy);
+          if (total == HW && planes_whole(vec, HW))
+            hipLaunchKernelGGL((bn_stats64_kernel<scalar_t>), grid, dim3(256),
+                               0, stream.stream(), x.data_ptr<scalar_t>(),
+                               out.data_ptr<double>(), N, C, HW, chunk);
+          else
+            hipLaunchKernelGGL((bn_stats64_span_kernel<scalar_t>), grid,
+                               dim3(256), 0, stream.stream(),
+                               x.data_ptr<scalar_t>(), out.data_ptr<double>(),
+                               N, C, HW, start, total, chunk);
         });
     return out;
   }
+  TORCH_CHECK(HW < (int64_t)1 << 30, "plane too large");
   const int64_t len = W - ml - mr;
-  const int64_t gy0 = (HW + chunk - 1) / chunk;
+  const int64_t gy0 = stats_grid(C, HW, HW, 0).second;
   const int64_t rpc = (Hr + gy0 - 1) / gy0;
   const int64_t gy = (Hr + rpc - 1) / rpc;
   const int64_t S = len / vec + 2;  // slots a row can touch, at most
@@ -2119,51 +1965,45 @@ torch::Tensor bn_stats64_region_acc(torch::Tensor x, torch::Tensor out,
   return out;
 }
 
+torch::Tensor bn_stats64_acc(torch::Tensor x, torch::Tensor out) {
+  return bn_stats64_region_acc(x, out, {0, 0, 0, 0});
+}
+
+torch::Tensor bn_stats64(torch::Tensor x) {
+  check_bn_x(x);
+  return bn_stats64_acc(
+      x, torch::zeros({2 * x.size(1)}, x.options().dtype(torch::kDouble)));
+}
+
 torch::Tensor bn_apply(torch::Tensor x, torch::Tensor mean,
                        torch::Tensor invstd, torch::Tensor w, torch::Tensor b,
                        bool relu) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
-  const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
-  const int64_t total = N * C * HW;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  if (HW % 8 != 0) {
-    x = aligned16(x);
-    auto y = torch::empty_like(x);
-    const int vec = 16 / (int)x.element_size();
-    AT_DISPATCH_FLOATING_TYPES_AND2(
-        at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
-        "bn_apply_ragged", [&] {
-          auto launch = [&](auto kern) {
-            hipLaunchKernelGGL(
-                kern, dim3(grid_for((total + vec - 1) / vec, 256)), dim3(256),
-                0, stream.stream(), x.data_ptr<scalar_t>(),
-                y.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-                invstd.data_ptr<float>(), w.data_ptr<float>(),
-                b.data_ptr<float>(), total, C, HW);
-          };
-          if (relu) launch(bn_apply_ragged_kernel<scalar_t, true>);
-          else launch(bn_apply_ragged_kernel<scalar_t, false>);
-        });
-    return y;
-  }
+  check_bn_x(x);
+  const int64_t C = x.size(1), HW = x.size(2) * x.size(3);
+  const int64_t total = x.numel();
+  check_bn_vec(mean, C, "mean");
+  check_bn_vec(invstd, C, "invstd");
+  check_bn_vec(w, C, "w");
+  check_bn_vec(b, C, "b");
+  x = slot_aligned(x);
   auto y = torch::empty_like(x);
+  const int64_t vec = 16 / (int64_t)x.element_size();
+  auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
       "bn_apply", [&] {
-        if (relu)
-          hipLaunchKernelGGL((bn_apply_kernel<scalar_t, true>),
-                             dim3(grid_for(total, 256)), dim3(256), 0,
-                             stream.stream(), x.data_ptr<scalar_t>(),
-                             y.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-                             invstd.data_ptr<float>(), w.data_ptr<float>(),
-                             b.data_ptr<float>(), N, C, HW);
-        else
-          hipLaunchKernelGGL((bn_apply_kernel<scalar_t, false>),
-                             dim3(grid_for(total, 256)), dim3(256), 0,
-                             stream.stream(), x.data_ptr<scalar_t>(),
-                             y.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-                             invstd.data_ptr<float>(), w.data_ptr<float>(),
-                             b.data_ptr<float>(), N, C, HW);
+        with_bool(relu, [&](auto relu_c) {
+          with_bool(planes_whole(vec, HW), [&](auto whole_c) {
+            hipLaunchKernelGGL(
+                (bn_apply_kernel<scalar_t, decltype(relu_c)::value,
+                                 decltype(whole_c)::value>),
+                dim3(grid_for((total + vec - 1) / vec, 256)), dim3(256), 0,
+                stream.stream(), x.data_ptr<scalar_t>(),
+                y.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+                invstd.data_ptr<float>(), w.data_ptr<float>(),
+                b.data_ptr<float>(), total, C, HW);
+          });
+        });
       });
   return y;
 }
@@ -2171,102 +2011,86 @@ torch::Tensor bn_apply(torch::Tensor x, torch::Tensor mean,
 torch::Tensor bn_bwd_stats(torch::Tensor go, torch::Tensor x, torch::Tensor y,
                            torch::Tensor mean, torch::Tensor invstd,
                            bool relu) {
+  check_bn_x(x);
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  check_bn_like(go, x, "go");
+  if (relu) check_bn_like(y, x, "y");
+  check_bn_vec(mean, C, "mean");
+  check_bn_vec(invstd, C, "invstd");
+  go = slot_aligned(go);
+  x = slot_aligned(x);
+  if (relu) y = slot_aligned(y);
   auto out = torch::zeros({2 * C}, x.options().dtype(torch::kDouble));
-  const int64_t splits = stats_splits(C, HW);
-  int64_t chunk = (HW + splits - 1) / splits;
-  chunk = ((chunk + 2047) / 2048) * 2048;
-  const int64_t gy = (HW + chunk - 1) / chunk;
+  const int64_t vec = 16 / (int64_t)x.element_size();
+  const auto cg = stats_grid(C, HW, HW, slot_slack(vec, HW, 0));
+  const int64_t chunk = cg.first, gy = cg.second;
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (HW % 8 != 0) {
-    TORCH_CHECK(go.is_contiguous() && x.is_contiguous() &&
-                (!relu || y.is_contiguous()));
-    go = aligned16(go);
-    x = aligned16(x);
-    if (relu) y = aligned16(y);
-    // chunk windows start at the plane's first slot: up to vec-1 elements
-    // before the plane
-    const int64_t vec = 16 / (int64_t)x.element_size();
-    const int64_t gyr = (HW + vec - 1 + chunk - 1) / chunk;
-    AT_DISPATCH_FLOATING_TYPES_AND2(
-        at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
-        "bn_bwd_stats_ragged", [&] {
-          auto launch = [&](auto kern) {
-            hipLaunchKernelGGL(
-                kern, dim3((uint32_t)C, (uint32_t)gyr), dim3(256), 0,
-                stream.stream(), go.data_ptr<scalar_t>(),
-                x.data_ptr<scalar_t>(),
-                relu ? y.data_ptr<scalar_t>() : (scalar_t*)nullptr,
-                mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                out.data_ptr<double>(), N, C, HW, chunk);
-          };
-          if (relu) launch(bn_bwd_stats_ragged_kernel<scalar_t, true>);
-          else launch(bn_bwd_stats_ragged_kernel<scalar_t, false>);
-        });
-    return out;
-  }
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
       "bn_bwd_stats", [&] {
-        if (relu)
-          hipLaunchKernelGGL((bn_bwd_stats_kernel<scalar_t, true>),
-                             dim3((uint32_t)C, (uint32_t)gy), dim3(256), 0,
-                             stream.stream(), go.data_ptr<scalar_t>(),
-                             x.data_ptr<scalar_t>(), y.data_ptr<scalar_t>(),
-                             mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                             out.data_ptr<double>(), N, C, HW, chunk);
-        else
-          hipLaunchKernelGGL((bn_bwd_stats_kernel<scalar_t, false>),
-                             dim3((uint32_t)C, (uint32_t)gy), dim3(256), 0,
-                             stream.stream(), go.data_ptr<scalar_t>(),
-                             x.data_ptr<scalar_t>(), (scalar_t*)nullptr,
-                             mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                             out.data_ptr<double>(), N, C, HW, chunk);
+        with_bool(relu, [&](auto relu_c) {
+          with_bool(planes_whole(vec, HW), [&](auto whole_c) {
+            hipLaunchKernelGGL(
+                (bn_bwd_stats_kernel<scalar_t, decltype(relu_c)::value,
+                                     decltype(whole_c)::value>),
+                dim3((uint32_t)C, (uint32_t)gy), dim3(256), 0, stream.stream(),
+                go.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
+                relu ? y.data_ptr<scalar_t>() : (scalar_t*)nullptr,
+                mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                out.data_ptr<double>(), N, C, HW, chunk);
+          });
+        });
       });
   return out;
 }
 
-// any-HW backward apply; `region` restricts the two reduction terms to
-// rows [row_lo,row_hi) x cols [col_lo,col_hi)
-static torch::Tensor bn_bwd_apply_ragged(torch::Tensor go, torch::Tensor x,
+// the launcher beneath bn_bwd_apply and bn_bwd_apply_region; `region`
+// restricts the two reduction terms to rows [row_lo,row_hi) x cols
+// [col_lo,col_hi)
+static torch::Tensor bn_bwd_apply_launch(torch::Tensor go, torch::Tensor x,
                                          torch::Tensor y, torch::Tensor mean,
                                          torch::Tensor invstd, torch::Tensor w,
                                          torch::Tensor gsum,
                                          torch::Tensor gxsum, double n,
                                          bool relu, bool region, int row_lo,
                                          int row_hi, int col_lo, int col_hi) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous() &&
-              go.is_contiguous() && go.sizes() == x.sizes() &&
-              (!relu || (y.is_contiguous() && y.sizes() == x.sizes())));
-  const int64_t N = x.size(0), C = x.size(1), W = x.size(3);
-  const int64_t HW = x.size(2) * W;
-  const int64_t total = N * C * HW;
-  go = aligned16(go);
-  x = aligned16(x);
-  if (relu) y = aligned16(y);
+  check_bn_x(x);
+  const int64_t C = x.size(1), W = x.size(3), HW = x.size(2) * W;
+  const int64_t total = x.numel();
+  check_bn_like(go, x, "go");
+  if (relu) check_bn_like(y, x, "y");
+  check_bn_vec(mean, C, "mean");
+  check_bn_vec(invstd, C, "invstd");
+  check_bn_vec(w, C, "w");
+  check_bn_vec(gsum, C, "gsum");
+  check_bn_vec(gxsum, C, "gxsum");
+  go = slot_aligned(go);
+  x = slot_aligned(x);
+  if (relu) y = slot_aligned(y);
   auto gi = torch::empty_like(x);
-  const int vec = 16 / (int)x.element_size();
+  const int64_t vec = 16 / (int64_t)x.element_size();
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
-      "bn_bwd_apply_ragged", [&] {
-        auto launch = [&](auto kern) {
-          hipLaunchKernelGGL(
-              kern, dim3(grid_for((total + vec - 1) / vec, 256)), dim3(256), 0,
-              stream.stream(), go.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
-              relu ? y.data_ptr<scalar_t>() : (scalar_t*)nullptr,
-              gi.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-              invstd.data_ptr<float>(), w.data_ptr<float>(),
-              gsum.data_ptr<float>(), gxsum.data_ptr<float>(), 1.0 / n, total,
-              C, HW, (int)W, row_lo, row_hi, col_lo, col_hi);
-        };
-        if (region) {
-          if (relu) launch(bn_bwd_apply_ragged_kernel<scalar_t, true, true>);
-          else launch(bn_bwd_apply_ragged_kernel<scalar_t, false, true>);
-        } else {
-          if (relu) launch(bn_bwd_apply_ragged_kernel<scalar_t, true, false>);
-          else launch(bn_bwd_apply_ragged_kernel<scalar_t, false, false>);
-        }
+      "bn_bwd_apply", [&] {
+        with_bool(relu, [&](auto relu_c) {
+          with_bool(region, [&](auto region_c) {
+            with_bool(planes_whole(vec, HW), [&](auto whole_c) {
+              hipLaunchKernelGGL(
+                  (bn_bwd_apply_kernel<scalar_t, decltype(relu_c)::value,
+                                       decltype(region_c)::value,
+                                       decltype(whole_c)::value>),
+                  dim3(grid_for((total + vec - 1) / vec, 256)), dim3(256), 0,
+                  stream.stream(), go.data_ptr<scalar_t>(),
+                  x.data_ptr<scalar_t>(),
+                  relu ? y.data_ptr<scalar_t>() : (scalar_t*)nullptr,
+                  gi.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+                  invstd.data_ptr<float>(), w.data_ptr<float>(),
+                  gsum.data_ptr<float>(), gxsum.data_ptr<float>(), 1.0 / n,
+                  total, C, HW, (int)W, row_lo, row_hi, col_lo, col_hi);
+            });
+          });
+        });
       });
   return gi;
 }
@@ -2275,36 +2099,8 @@ torch::Tensor bn_bwd_apply(torch::Tensor go, torch::Tensor x, torch::Tensor y,
                            torch::Tensor mean, torch::Tensor invstd,
                            torch::Tensor w, torch::Tensor gsum,
                            torch::Tensor gxsum, double n, bool relu) {
-  const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
-  if (HW % 8 != 0)
-    return bn_bwd_apply_ragged(go, x, y, mean, invstd, w, gsum, gxsum, n, relu,
-                               false, 0, 0, 0, 0);
-  auto gi = torch::empty_like(x);
-  const int64_t total = N * C * HW;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  AT_DISPATCH_FLOATING_TYPES_AND2(
-      at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
-      "bn_bwd_apply", [&] {
-        if (relu)
-          hipLaunchKernelGGL(
-              (bn_bwd_apply_kernel<scalar_t, true>),
-              dim3(grid_for(total, 256)), dim3(256), 0, stream.stream(),
-              go.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
-              y.data_ptr<scalar_t>(), gi.data_ptr<scalar_t>(),
-              mean.data_ptr<float>(), invstd.data_ptr<float>(),
-              w.data_ptr<float>(), gsum.data_ptr<float>(),
-              gxsum.data_ptr<float>(), 1.0 / n, N, C, HW);
-        else
-          hipLaunchKernelGGL(
-              (bn_bwd_apply_kernel<scalar_t, false>),
-              dim3(grid_for(total, 256)), dim3(256), 0, stream.stream(),
-              go.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),
-              (scalar_t*)nullptr, gi.data_ptr<scalar_t>(),
-              mean.data_ptr<float>(), invstd.data_ptr<float>(),
-              w.data_ptr<float>(), gsum.data_ptr<float>(),
-              gxsum.data_ptr<float>(), 1.0 / n, N, C, HW);
-      });
-  return gi;
+  return bn_bwd_apply_launch(go, x, y, mean, invstd, w, gsum, gxsum, n, relu,
+                             false, 0, 0, 0, 0);
 }
 
 // bn_bwd_apply when mean/var were taken over the region only
@@ -2315,13 +2111,12 @@ torch::Tensor bn_bwd_apply_region(torch::Tensor go, torch::Tensor x,
                                   torch::Tensor gsum, torch::Tensor gxsum,
                                   double n, bool relu,
                                   std::vector<int64_t> margin) {
-  TORCH_CHECK(x.dim() == 4);
+  check_bn_x(x);
   const int64_t H = x.size(2), W = x.size(3);
   check_margin(margin, H, W);
-  if (margin[0] + margin[1] + margin[2] + margin[3] == 0)
-    return bn_bwd_apply(go, x, y, mean, invstd, w, gsum, gxsum, n, relu);
-  return bn_bwd_apply_ragged(go, x, y, mean, invstd, w, gsum, gxsum, n, relu,
-                             true, (int)margin[0], (int)(H - margin[1]),
+  const bool region = margin[0] + margin[1] + margin[2] + margin[3] != 0;
+  return bn_bwd_apply_launch(go, x, y, mean, invstd, w, gsum, gxsum, n, relu,
+                             region, (int)margin[0], (int)(H - margin[1]),
                              (int)margin[2], (int)(W - margin[3]));
 }
 

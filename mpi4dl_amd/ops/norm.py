@@ -157,10 +157,7 @@ class TileBatchNorm2d(nn.BatchNorm2d):
             if buf is None or buf.device != x.device or buf.numel() != 2 * C:
                 buf = torch.zeros(2 * C, device=x.device, dtype=torch.float64)
                 self._stats64 = buf
-            if any(mg) or (H * W) % 8:
-                stats = ge.bn_stats64_region_acc(x, buf, list(mg))
-            else:
-                stats = ge.bn_stats64_acc(x, buf)
+            stats = ge.bn_stats64_region_acc(x, buf, list(mg))
             if group is not None:
                 dist.all_reduce(stats, group=group)
                 n *= dist.get_world_size(group=group)

@@ -1,7 +1,8 @@
-"""GPU (MI355X) tests of the ragged / region BatchNorm kernels: region
-statistics, TileBatchNorm2d with ``stat_margin`` and with planes whose
-H*W is no multiple of 8, against references computed from the same,
-already rounded inputs."""
+"""GPU (MI355X) tests of the BatchNorm kernels: region statistics,
+TileBatchNorm2d with ``stat_margin`` and with planes whose H*W is no
+multiple of 8, against references computed from the same, already
+rounded inputs; and the bindings called directly on ragged, whole-slot
+and misaligned tensors."""
 
 import pytest
 import torch
@@ -223,3 +224,189 @@ def test_aligned_case_unchanged():
     assert torch.equal(x.grad, gi_old)
     assert torch.equal(bn.bias.grad, bst[:C])
     assert torch.equal(bn.weight.grad, bst[C:])
+
+
+# -- one kernel family for every plane shape: the bindings called directly --
+
+def _bn_inputs(shape, dtype, seed):
+    """Seeded x, go, y of ``shape`` plus the per-channel vectors and n, on
+    cuda. x and go are offset from zero so that no per-channel sum comes
+    out near zero (checked by _assert_no_cancellation)."""
+    g = torch.Generator().manual_seed(seed)
+    C = shape[1]
+    t = {
+        "x": (torch.randn(shape, generator=g) + 0.5).to(dtype),
+        "go": (torch.randn(shape, generator=g) + 0.5).to(dtype),
+        "y": torch.randn(shape, generator=g).to(dtype),
+        "mean": torch.randn(C, generator=g) * 0.3,
+        "invstd": torch.rand(C, generator=g) + 0.5,
+        "w": torch.rand(C, generator=g) + 0.5,
+        "b": torch.randn(C, generator=g) * 0.3,
+        "gsum": torch.randn(C, generator=g),
+        "gxsum": torch.randn(C, generator=g),
+    }
+    return {k: v.cuda() for k, v in t.items()}
+
+
+def _ref_bwd_stats(go, x, y, mean, invstd, relu):
+    """[gsum, gxsum]: products formed in fp32 as the kernel forms them,
+    summed in fp64."""
+    g = go.float()
+    if relu:
+        g = torch.where(y.float() <= 0, torch.zeros_like(g), g)
+    xh = (x.float() - mean.view(1, -1, 1, 1)) * invstd.view(1, -1, 1, 1)
+    return torch.cat([
+        g.double().sum(dim=(0, 2, 3)), (g * xh).double().sum(dim=(0, 2, 3))
+    ])
+
+
+def _assert_no_cancellation(ref):
+    """rtol=1e-10 with atol=0 only means something away from zero."""
+    assert float(ref.abs().min()) >= 0.1, ref
+
+
+def _close(a, b):
+    return torch.allclose(a, b, rtol=1e-10, atol=0)
+
+
+@gpu
+@requires_gpu
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_layout_independence(dtype, relu):
+    """The same 7x9 planes as a ragged tensor (HW = 63: slots straddle the
+    plane seams, the flat size 378 ends in a partial slot) and as the top
+    rows of an 8x9 tensor (HW = 72: whole slots) give the same bits
+    elementwise and the same sums."""
+    from mpi4dl_amd.ops import backend
+
+    ge = backend.ext()
+    a = _bn_inputs((2, 3, 8, 9), dtype, seed=0)
+    r = {k: v[:, :, :7].contiguous() if v.dim() == 4 else v
+         for k, v in a.items()}
+    vec = [a[k] for k in ("mean", "invstd", "w")]
+    n = float(2 * 63)
+    top = [0, 1, 0, 0]  # margin that leaves rows 0..6 of the 8x9 plane
+
+    y_r = ge.bn_apply(r["x"], *vec, a["b"], relu)
+    y_a = ge.bn_apply(a["x"], *vec, a["b"], relu)
+    assert torch.equal(y_a[:, :, :7], y_r)
+
+    gi_r = ge.bn_bwd_apply(r["go"], r["x"], r["y"], *vec, a["gsum"],
+                           a["gxsum"], n, relu)
+    gi_a = ge.bn_bwd_apply(a["go"], a["x"], a["y"], *vec, a["gsum"],
+                           a["gxsum"], n, relu)
+    gi_m = ge.bn_bwd_apply_region(a["go"], a["x"], a["y"], *vec, a["gsum"],
+                                  a["gxsum"], n, relu, top)
+    assert torch.equal(gi_a[:, :, :7], gi_r)
+    assert torch.equal(gi_m[:, :, :7], gi_r)
+
+    def zeros():
+        return torch.zeros(6, device="cuda", dtype=torch.float64)
+
+    want = _ref_stats(r["x"], (0, 0, 0, 0))
+    _assert_no_cancellation(want)
+    st_r = ge.bn_stats64_region_acc(r["x"], zeros(), [0, 0, 0, 0])
+    st_m = ge.bn_stats64_region_acc(a["x"], zeros(), top)
+    st_acc = ge.bn_stats64_acc(r["x"], zeros())
+    for got in (st_r, st_m, st_acc):
+        assert _close(got, want), (got - want).abs().max()
+    assert _close(st_m, st_r) and _close(st_acc, st_r)
+
+    want = _ref_bwd_stats(r["go"], r["x"], r["y"], a["mean"], a["invstd"], relu)
+    _assert_no_cancellation(want)
+    go_z = a["go"].clone()
+    go_z[:, :, 7] = 0
+    bs_r = ge.bn_bwd_stats(r["go"], r["x"], r["y"], a["mean"], a["invstd"], relu)
+    bs_a = ge.bn_bwd_stats(go_z, a["x"], a["y"], a["mean"], a["invstd"], relu)
+    assert _close(bs_r, want), (bs_r - want).abs().max()
+    assert _close(bs_a, want), (bs_a - want).abs().max()
+    assert _close(bs_a, bs_r)
+
+
+@gpu
+@requires_gpu
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_whole_slot_planes_three_chunks(dtype):
+    """HW = 4608 with C = 3: whole-slot planes, three chunks per channel,
+    the last one partial."""
+    from mpi4dl_amd.ops import backend
+
+    ge = backend.ext()
+    t = _bn_inputs((1, 3, 64, 72), dtype, seed=1)
+    want = _ref_stats(t["x"], (0, 0, 0, 0))
+    _assert_no_cancellation(want)
+    got = ge.bn_stats64_acc(
+        t["x"], torch.zeros(6, device="cuda", dtype=torch.float64))
+    assert _close(got, want), (got - want).abs().max()
+    for relu in (False, True):
+        want = _ref_bwd_stats(t["go"], t["x"], t["y"], t["mean"], t["invstd"],
+                              relu)
+        _assert_no_cancellation(want)
+        got = ge.bn_bwd_stats(t["go"], t["x"], t["y"], t["mean"], t["invstd"],
+                              relu)
+        assert _close(got, want), (relu, (got - want).abs().max())
+
+
+@gpu
+@requires_gpu
+def test_misaligned_base():
+    """Contiguous tensors whose data starts 2 bytes off the 16-byte grid
+    give what their clones give."""
+    from mpi4dl_amd.ops import backend
+
+    ge = backend.ext()
+    shape = (2, 3, 8, 8)
+    t = _bn_inputs(shape, torch.bfloat16, seed=2)
+    off = {}
+    for k in ("x", "go", "y"):
+        big = torch.empty(t[k].numel() + 8, device="cuda", dtype=torch.bfloat16)
+        off[k] = big[1:1 + t[k].numel()].view(shape)
+        off[k].copy_(t[k])
+        assert off[k].is_contiguous() and off[k].data_ptr() % 16 == 2
+    vec = [t[k] for k in ("mean", "invstd", "w")]
+    n = float(2 * 64)
+    cl = {k: v.clone() for k, v in off.items()}
+    assert all(v.data_ptr() % 16 == 0 for v in cl.values())
+
+    def both(fn):
+        return fn(off), fn(cl)
+
+    for relu in (False, True):
+        def bwd(fn, *extra):
+            return both(lambda s: fn(s["go"], s["x"], s["y"], *vec, t["gsum"],
+                                     t["gxsum"], n, relu, *extra))
+
+        got, want = both(lambda s: ge.bn_apply(s["x"], *vec, t["b"], relu))
+        assert torch.equal(got, want)
+        got, want = bwd(ge.bn_bwd_apply)
+        assert torch.equal(got, want)
+        got, want = bwd(ge.bn_bwd_apply_region, [1, 0, 2, 1])
+        assert torch.equal(got, want)
+        got, want = both(lambda s: ge.bn_bwd_stats(
+            s["go"], s["x"], s["y"], t["mean"], t["invstd"], relu))
+        assert _close(got, want)
+    got, want = both(lambda s: ge.bn_stats64_acc(
+        s["x"], torch.zeros(6, device="cuda", dtype=torch.float64)))
+    assert _close(got, want)
+
+
+@gpu
+@requires_gpu
+def test_bn_bindings_reject_bad_input():
+    """Shapes, lengths and layouts are checked before any launch."""
+    from mpi4dl_amd.ops import backend
+
+    ge = backend.ext()
+    t = _bn_inputs((2, 3, 8, 8), torch.bfloat16, seed=3)
+    vec = [t[k] for k in ("mean", "invstd", "w")]
+    with pytest.raises(RuntimeError):
+        ge.bn_bwd_apply(t["go"][:, :, :4].contiguous(), t["x"], t["y"], *vec,
+                        t["gsum"], t["gxsum"], 128.0, False)
+    with pytest.raises(RuntimeError):
+        ge.bn_apply(t["x"], torch.zeros(4, device="cuda"), t["invstd"],
+                    t["w"], t["b"], False)
+    go_nc = t["go"].transpose(2, 3)
+    assert not go_nc.is_contiguous() and go_nc.shape == t["x"].shape
+    with pytest.raises(RuntimeError):
+        ge.bn_bwd_stats(go_nc, t["x"], t["y"], t["mean"], t["invstd"], False)
