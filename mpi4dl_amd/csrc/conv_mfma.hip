@@ -154,7 +154,8 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(
           }
         }
       }
-      // B image (tr-read layout, semantics measured by tr16_probe):
+      // B image (tr-read layout; the ds_read_b64_tr_b16 semantics are
+      // written down in profiles/PERF_NOTES.md):
       // element (k, px) of 16-px block pb lives at block-local offset
       //   (k>>3)*128 + ((k>>2)&1)*64 + (k&3)*16 + px
       // so this 8-pixel chunk is 16 CONTIGUOUS bytes (one ds_write_b128),
@@ -761,41 +762,6 @@ torch::Tensor conv_bwd_weight(torch::Tensor go, torch::Tensor x,
   return gw.view({(int64_t)K, (int64_t)C, R, S});
 }
 
-// ---------------------------------------------------------------------------
-// ds_read_b64_tr_b16 semantics probe: LDS holds arange shorts; each lane
-// does one tr read with a configurable per-lane address pattern; output
-// [64][4] shows exactly which LDS elements land in which lane/elem.
-// ---------------------------------------------------------------------------
-
-__global__ void tr16_probe_kernel(short* __restrict__ out, int mode) {
-  __shared__ __attribute__((aligned(16))) short lds[1024];
-  for (int i = threadIdx.x; i < 1024; i += blockDim.x) lds[i] = (short)i;
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    const int l = threadIdx.x;
-    int off;
-    if (mode == 0) off = 0;                               // uniform
-    else if (mode == 1) off = (l & 15) + ((l >> 4) << 6); // my assumed map
-    else if (mode == 2) off = l * 4;                      // linear x4
-    else off = (l & 15) * 4 + ((l >> 4) << 6);            // 4-elem rows
-    s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(
-            (__attribute__((address_space(3))) short*)lds + off));
-#pragma unroll
-    for (int e = 0; e < 4; ++e) out[l * 4 + e] = v[e];
-  }
-}
-
-torch::Tensor tr16_probe(int64_t mode) {
-  auto out = torch::zeros({64, 4}, torch::TensorOptions()
-                                       .dtype(torch::kShort)
-                                       .device(torch::kCUDA));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(tr16_probe_kernel, dim3(1), dim3(64), 0, stream.stream(),
-                     out.data_ptr<short>(), (int)mode);
-  return out;
-}
-
 }  // namespace conv_mfma
 
 void register_conv_mfma(pybind11::module_& m) {
@@ -803,6 +769,4 @@ void register_conv_mfma(pybind11::module_& m) {
         "implicit-GEMM MFMA conv forward (bf16 NCHW)");
   m.def("conv_bwd_weight", &conv_mfma::conv_bwd_weight,
         "implicit-GEMM MFMA conv weight gradient (fp32 out)");
-  m.def("tr16_probe", &conv_mfma::tr16_probe,
-        "ds_read_b64_tr_b16 lane-mapping probe");
 }

@@ -6,9 +6,11 @@ Kernel families (csrc/):
   weight-grad; stride-1 data-grad = the forward kernel on C<->K
   transposed / 180-rotated weights; STRIDED data-grad = zero-stuffed
   transposed conv through the same stride-1 kernel.
-* conv_pw.hip — the 1x1 family: skinny/fat/fat256 streaming GEMMs,
-  stride-2 gather + scatter backward-data, NT-GEMM bwd-weight with
-  pixel-slab split-K.
+* conv_pw.hip — the 1x1 family: the skinny streaming GEMM
+  (pw_kernel), the fat one at a 128- or 256-square tile
+  (pw_fat_kernel<4|8>), stride-2 gather + scatter backward-data, and
+  the NT-GEMM bwd-weight with pixel-slab split-K at the same two
+  tiles (pw_bwdw_kernel<4|8>).
 
 Per-shape, per-LEG policy (all crossovers measured on MI355X —
 profiles/PERF_NOTES.md): stride-2 1x1s, K<=64 1x1s, stems, wide

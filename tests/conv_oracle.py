@@ -114,13 +114,13 @@ def leg_is_bf16(leg):
 # ---------------------------------------------------------------------------
 # Host-side dispatch, transcribed. References are to the sources as of
 # this file's commit:
-#   conv_fwd        mpi4dl_amd/csrc/conv_mfma.hip:693-724 (v2 predicate,
+#   conv_fwd        mpi4dl_amd/csrc/conv_mfma.hip:694-725 (v2 predicate,
 #                   mfrag, the S*10+mfrag switch)
-#   launch_pw       mpi4dl_amd/csrc/conv_pw.hip:1151-1219 (fat256, fat,
+#   launch_pw       mpi4dl_amd/csrc/conv_pw.hip:661-696 (fat256, fat,
 #                   skinny mfrag, stride template)
-#   pw_bwdw         mpi4dl_amd/csrc/conv_pw.hip:1099-1105 (`big`, slab loop)
-#   ConvFn          mpi4dl_amd/ops/conv_native.py:56-171
-#   _pw_geom_ok     mpi4dl_amd/ops/conv_native.py:39-51
+#   pw_bwdw         mpi4dl_amd/csrc/conv_pw.hip:641-647 (`big`, slab loop)
+#   ConvFn          mpi4dl_amd/ops/conv_native.py:58-173
+#   _pw_geom_ok     mpi4dl_amd/ops/conv_native.py:41-53
 # ---------------------------------------------------------------------------
 
 def _mfrag(K):
@@ -347,8 +347,9 @@ def _build_cases():
     cases.append(Case("c36k24-n1", "pw_fwd", "pw<1,1>", 36, 24, 8, 16,
                       bias=True, N=1))
     # the same family through autograd: gx is the mirror GEMM (C <-> K),
-    # gw the unsplit 128-tile pw_bwdw at OHW = 128
-    for C, K in ((8, 24), (36, 48), (40, 104), (64, 136)):
+    # gw the unsplit 128-tile pw_bwdw at OHW = 128; (136, 136) gives it
+    # two K tiles and two C tiles, both with tails
+    for C, K in ((8, 24), (36, 48), (40, 104), (64, 136), (136, 136)):
         cases.append(Case(
             f"c{C}k{K}", "autograd",
             f"pw<{_mfrag(K)},1>+pw<{_mfrag(C)},1>+pw_bwdw128", C, K, 8, 16,
