@@ -33,6 +33,7 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include <cstdint>
+#include <string>
 
 namespace conv_mfma {
 
@@ -534,7 +535,7 @@ __global__ __launch_bounds__(256) void conv_bwdw_kernel(
   const int crs0 = nt * WBN;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wid = tid >> 6;  // 4 waves (2x2): wave tile 32x32? -> use 2x2 of 16
+  const int wid = tid >> 6;  // 4 waves (2x2); a wave owns 32x32 = 2x2 of 16x16
   const int wm = wid >> 1, wn = wid & 1;
 
   __shared__ __attribute__((aligned(16))) short lds[WBM * (WBK + 8) +
@@ -650,22 +651,57 @@ __global__ __launch_bounds__(256) void conv_bwdw_kernel(
 // Host wrappers
 // ---------------------------------------------------------------------------
 
-static ConvGeom make_geom(const torch::Tensor& x, const torch::Tensor& w,
-                          int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
+static ConvGeom make_geom(int64_t N, int64_t C, int64_t H, int64_t W,
+                          int64_t K, int64_t R, int64_t S, int64_t sh,
+                          int64_t sw, int64_t ph, int64_t pw) {
+  TORCH_CHECK(sh > 0 && sw > 0, "conv: stride must be positive");
   ConvGeom g;
-  g.N = (int)x.size(0);
-  g.C = (int)x.size(1);
-  g.H = (int)x.size(2);
-  g.W = (int)x.size(3);
-  g.K = (int)w.size(0);
-  g.R = (int)w.size(2);
-  g.S = (int)w.size(3);
+  g.N = (int)N; g.C = (int)C; g.H = (int)H; g.W = (int)W;
+  g.K = (int)K; g.R = (int)R; g.S = (int)S;
   g.sh = (int)sh; g.sw = (int)sw; g.ph = (int)ph; g.pw = (int)pw;
   g.OH = (g.H + 2 * g.ph - g.R) / g.sh + 1;
   g.OW = (g.W + 2 * g.pw - g.S) / g.sw + 1;
   g.CRS = g.C * g.R * g.S;
   g.row_tiles = (g.OW + BN - 1) / BN;
   return g;
+}
+
+// The forward kernel of a problem: the only place that decides it.
+struct FwdChoice {
+  using Kern = void (*)(const bf16*, const bf16*, const float*, bf16*,
+                        ConvGeom);
+  Kern kern;
+  int mfrag;  // v2: BM = 32 * mfrag; 0: the v1 kernel
+  std::string label;
+};
+
+static FwdChoice choose_fwd(const ConvGeom& g) {
+  static const FwdChoice::Kern v2[3][3] = {
+      {conv_fwd_v2_kernel<3, 1>, conv_fwd_v2_kernel<3, 2>,
+       conv_fwd_v2_kernel<3, 4>},
+      {conv_fwd_v2_kernel<7, 1>, conv_fwd_v2_kernel<7, 2>,
+       conv_fwd_v2_kernel<7, 4>},
+      {conv_fwd_v2_kernel<1, 1>, conv_fwd_v2_kernel<1, 2>,
+       conv_fwd_v2_kernel<1, 4>}};
+  // v2 exists for S in {1, 3, 7} only: its fast path keeps a 16- or
+  // 24-element row segment in registers and writes SS compile-time
+  // shifted copies of it. Every other kernel width runs the fully
+  // guarded v1 kernel.
+  const int si = (g.S == 3) ? 0 : (g.S == 7) ? 1 : (g.S == 1) ? 2 : -1;
+  const int64_t OHW = (int64_t)g.OH * g.OW;
+  if (!(g.sh == 1 && g.sw == 1 && si >= 0 && g.C * g.S >= BK &&
+        OHW % BN == 0 && g.OW % 8 == 0))
+    return {conv_fwd_kernel, 0, "v1"};
+  // M-adaptive BM (32/64/128 by K)
+  const int mi = (g.K <= 32) ? 0 : (g.K <= 64) ? 1 : 2;
+  return {v2[si][mi], 1 << mi,
+          "v2<" + std::to_string(g.S) + "," + std::to_string(1 << mi) + ">"};
+}
+
+std::string conv_fwd_kernel_name(int64_t C, int64_t K, int64_t H, int64_t W,
+                                 int64_t R, int64_t S, int64_t sh, int64_t sw,
+                                 int64_t ph, int64_t pw) {
+  return choose_fwd(make_geom(1, C, H, W, K, R, S, sh, sw, ph, pw)).label;
 }
 
 torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor w,
@@ -676,7 +712,8 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor w,
               w.scalar_type() == torch::kBFloat16,
               "conv_fwd: bf16 only");
   TORCH_CHECK(x.size(1) == w.size(1), "channel mismatch");
-  ConvGeom g = make_geom(x, w, sh, sw, ph, pw);
+  ConvGeom g = make_geom(x.size(0), x.size(1), x.size(2), x.size(3),
+                         w.size(0), w.size(2), w.size(3), sh, sw, ph, pw);
   auto out = torch::empty({g.N, g.K, g.OH, g.OW},
                           x.options().dtype(torch::kBFloat16));
   const float* bptr = nullptr;
@@ -686,51 +723,27 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor w,
     bptr = b32.data_ptr<float>();
   }
   auto stream = at::cuda::getCurrentCUDAStream();
-  const int64_t OHW = (int64_t)g.OH * g.OW;
-  // v2 exists for S in {1, 3, 7} only: its fast path keeps a 16- or
-  // 24-element row segment in registers and writes SS compile-time
-  // shifted copies of it. Every other kernel width runs the fully
-  // guarded v1 kernel below.
-  const bool v2_width = (g.S == 1 || g.S == 3 || g.S == 7);
-  if (g.sh == 1 && g.sw == 1 && v2_width && g.C * g.S >= BK &&
-      OHW % BN == 0 && g.OW % 8 == 0) {
-    // v2: row-pass kernel with [K][R][C*S]-permuted weights; global
-    // pixel axis + M-adaptive BM (32/64/128 by K)
-    auto w2 = w.view({g.K, g.C, g.R, g.S})
-                  .permute({0, 2, 1, 3})
-                  .reshape({g.K, g.R, (int64_t)g.C * g.S})
-                  .contiguous();
-    const int mfrag = (g.K <= 32) ? 1 : (g.K <= 64) ? 2 : 4;
-    const int m_tiles2 = (g.K + 32 * mfrag - 1) / (32 * mfrag);
-    const int64_t blocks2 = (int64_t)m_tiles2 * (OHW / BN) * g.N;
-    TORCH_CHECK(blocks2 > 0 && blocks2 < (1LL << 31), "grid too large");
-    auto launch_v2 = [&](auto* kern) {
-      hipLaunchKernelGGL(kern, dim3((uint32_t)blocks2), dim3(256), 0,
-                         stream.stream(), (const bf16*)x.data_ptr(),
-                         (const bf16*)w2.data_ptr(), bptr,
-                         (bf16*)out.data_ptr(), g);
-    };
-    switch (g.S * 10 + mfrag) {
-      case 31: launch_v2(conv_fwd_v2_kernel<3, 1>); break;
-      case 32: launch_v2(conv_fwd_v2_kernel<3, 2>); break;
-      case 34: launch_v2(conv_fwd_v2_kernel<3, 4>); break;
-      case 71: launch_v2(conv_fwd_v2_kernel<7, 1>); break;
-      case 72: launch_v2(conv_fwd_v2_kernel<7, 2>); break;
-      case 74: launch_v2(conv_fwd_v2_kernel<7, 4>); break;
-      case 11: launch_v2(conv_fwd_v2_kernel<1, 1>); break;
-      case 12: launch_v2(conv_fwd_v2_kernel<1, 2>); break;
-      case 14: launch_v2(conv_fwd_v2_kernel<1, 4>); break;
-      default:
-        TORCH_CHECK(false, "conv_fwd: no v2 kernel for S=", g.S);
-    }
-    return out;
+  const FwdChoice ch = choose_fwd(g);
+  torch::Tensor wk = w;
+  int64_t blocks;
+  if (ch.mfrag) {
+    // v2: row-pass kernel with [K][R][C*S]-permuted weights over the
+    // global pixel axis
+    wk = w.view({g.K, g.C, g.R, g.S})
+             .permute({0, 2, 1, 3})
+             .reshape({g.K, g.R, (int64_t)g.C * g.S})
+             .contiguous();
+    const int m_tiles = (g.K + 32 * ch.mfrag - 1) / (32 * ch.mfrag);
+    blocks = (int64_t)m_tiles * ((int64_t)g.OH * g.OW / BN) * g.N;
+    TORCH_CHECK(blocks > 0, "grid too large");
+  } else {
+    const int m_tiles = (g.K + BM - 1) / BM;
+    blocks = (int64_t)m_tiles * g.row_tiles * g.OH * g.N;
   }
-  const int m_tiles = (g.K + BM - 1) / BM;
-  const int64_t blocks = (int64_t)m_tiles * g.row_tiles * g.OH * g.N;
   TORCH_CHECK(blocks < (1LL << 31), "grid too large");
-  hipLaunchKernelGGL(conv_fwd_kernel, dim3((uint32_t)blocks), dim3(256), 0,
+  hipLaunchKernelGGL(ch.kern, dim3((uint32_t)blocks), dim3(256), 0,
                      stream.stream(), (const bf16*)x.data_ptr(),
-                     (const bf16*)w.data_ptr(), bptr, (bf16*)out.data_ptr(),
+                     (const bf16*)wk.data_ptr(), bptr, (bf16*)out.data_ptr(),
                      g);
   return out;
 }
@@ -741,17 +754,13 @@ torch::Tensor conv_bwd_weight(torch::Tensor go, torch::Tensor x,
   TORCH_CHECK(go.is_cuda() && go.is_contiguous() && x.is_contiguous());
   TORCH_CHECK(go.scalar_type() == torch::kBFloat16 &&
               x.scalar_type() == torch::kBFloat16);
-  const int K = (int)go.size(1), C = (int)x.size(1);
-  ConvGeom g;
-  g.N = (int)x.size(0); g.C = C; g.H = (int)x.size(2); g.W = (int)x.size(3);
-  g.K = K; g.R = (int)R; g.S = (int)S;
-  g.sh = (int)sh; g.sw = (int)sw; g.ph = (int)ph; g.pw = (int)pw;
-  g.OH = (int)go.size(2); g.OW = (int)go.size(3);
-  g.CRS = C * (int)R * (int)S;
-  g.row_tiles = 0;
-  auto gw = torch::zeros({(int64_t)K, (int64_t)g.CRS},
+  const ConvGeom g = make_geom(x.size(0), x.size(1), x.size(2), x.size(3),
+                               go.size(1), R, S, sh, sw, ph, pw);
+  TORCH_CHECK(go.size(0) == g.N && go.size(2) == g.OH && go.size(3) == g.OW,
+              "conv_bwd_weight: go is not the gradient of this convolution");
+  auto gw = torch::zeros({(int64_t)g.K, (int64_t)g.CRS},
                          x.options().dtype(torch::kFloat));
-  const int m_tiles = (K + WBM - 1) / WBM;
+  const int m_tiles = (g.K + WBM - 1) / WBM;
   const int n_tiles = (g.CRS + WBN - 1) / WBN;
   const int64_t blocks = (int64_t)m_tiles * n_tiles * g.N * g.OH;
   TORCH_CHECK(blocks < (1LL << 31), "grid too large");
@@ -759,7 +768,7 @@ torch::Tensor conv_bwd_weight(torch::Tensor go, torch::Tensor x,
   hipLaunchKernelGGL(conv_bwdw_kernel, dim3((uint32_t)blocks), dim3(256), 0,
                      stream.stream(), (const bf16*)go.data_ptr(),
                      (const bf16*)x.data_ptr(), gw.data_ptr<float>(), g);
-  return gw.view({(int64_t)K, (int64_t)C, R, S});
+  return gw.view({(int64_t)g.K, (int64_t)g.C, R, S});
 }
 
 }  // namespace conv_mfma
@@ -769,4 +778,7 @@ void register_conv_mfma(pybind11::module_& m) {
         "implicit-GEMM MFMA conv forward (bf16 NCHW)");
   m.def("conv_bwd_weight", &conv_mfma::conv_bwd_weight,
         "implicit-GEMM MFMA conv weight gradient (fp32 out)");
+  m.def("conv_fwd_kernel_name", &conv_mfma::conv_fwd_kernel_name,
+        "label of the kernel conv_fwd launches for (C, K, H, W, R, S, sh, "
+        "sw, ph, pw); no tensor, no HIP call");
 }

@@ -34,6 +34,7 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include <cstdint>
+#include <string>
 
 namespace conv_pw {
 
@@ -622,6 +623,43 @@ static void launch(Kern kern, int64_t blocks, int threads, Args... args) {
                      at::cuda::getCurrentCUDAStream().stream(), args...);
 }
 
+// The bwd-weight kernel, tile and pixel slab of a problem: the only
+// place that decides them.
+struct BwdwChoice {
+  void (*kern)(const bf16*, const bf16*, float*, BwGeom);
+  int tile;       // square block tile over (K, C)
+  int slab;       // pixels per block (divides OHW)
+  int64_t blocks;
+  std::string label;
+};
+
+static BwdwChoice choose_bwdw(int64_t Nimg, int K, int C, int OHW) {
+  // 256 tile only when the pixel dim is deep enough that k-steps stay
+  // long after slab splitting (small-P shapes measured 0.5x with deep
+  // splits: 2-kstep blocks are staging-latency bound and the 256x256
+  // fp32 atomic tiles dominate)
+  const bool big = (K >= 256 && C >= 256 && OHW >= 16384);
+  const int tile = big ? 256 : 128;
+  const int64_t mn =
+      (int64_t)((K + tile - 1) / tile) * ((C + tile - 1) / tile);
+  int slab = OHW;
+  while (slab > 512 && mn * Nimg * (OHW / slab) < 384 && slab % 2 == 0 &&
+         (slab / 2) % 64 == 0)
+    slab /= 2;
+  // measured: at the 256 tile a BK=32 3-buffer span pipeline was 0.96x of
+  // this BK=64 2-buffer form (halving the MFMA work per barrier cancels
+  // the span win); see profiles/PERF_NOTES.md
+  return {big ? pw_bwdw_kernel<8> : pw_bwdw_kernel<4>, tile, slab,
+          mn * Nimg * (OHW / slab),
+          "pw_bwdw" + std::to_string(tile) + (slab < OHW ? ":slab" : "")};
+}
+
+std::string pw_bwdw_kernel_name(int64_t N, int64_t K, int64_t C,
+                                int64_t OHW) {
+  TORCH_CHECK(OHW > 0, "pw_bwdw_kernel_name: OHW");
+  return choose_bwdw(N, (int)K, (int)C, (int)OHW).label;
+}
+
 torch::Tensor pw_bwdw(torch::Tensor go, torch::Tensor x) {
   TORCH_CHECK(go.is_cuda() && go.is_contiguous() && x.is_contiguous());
   TORCH_CHECK(go.scalar_type() == torch::kBFloat16 &&
@@ -634,65 +672,64 @@ torch::Tensor pw_bwdw(torch::Tensor go, torch::Tensor x) {
   g.C = (int)x.size(1);
   g.OHW = (int)(go.size(2) * go.size(3));
   TORCH_CHECK(g.OHW % 64 == 0, "pw_bwdw: OHW % 64");
-  // 256 tile only when the pixel dim is deep enough that k-steps stay
-  // long after slab splitting (small-P shapes measured 0.5x with deep
-  // splits: 2-kstep blocks are staging-latency bound and the 256x256
-  // fp32 atomic tiles dominate)
-  const bool big = (g.K >= 256 && g.C >= 256 && g.OHW >= 16384);
-  const int tile = big ? 256 : 128;
-  const int mn = ((g.K + tile - 1) / tile) * ((g.C + tile - 1) / tile);
-  int slab = g.OHW;
-  while (slab > 512 && (int64_t)mn * g.Nimg * (g.OHW / slab) < 384 &&
-         slab % 2 == 0 && (slab / 2) % 64 == 0)
-    slab /= 2;
+  const BwdwChoice ch = choose_bwdw(g.Nimg, g.K, g.C, g.OHW);
+  g.slab = ch.slab;
   auto gw = torch::zeros({(int64_t)g.K, (int64_t)g.C},
                          x.options().dtype(torch::kFloat));
-  g.slab = slab;
-  // measured: at the 256 tile a BK=32 3-buffer span pipeline was 0.96x of
-  // this BK=64 2-buffer form (halving the MFMA work per barrier cancels
-  // the span win); see profiles/PERF_NOTES.md
-  launch(big ? pw_bwdw_kernel<8> : pw_bwdw_kernel<4>,
-         (int64_t)mn * g.Nimg * (g.OHW / slab), 2 * tile,
-         (const bf16*)go.data_ptr(), (const bf16*)x.data_ptr(),
-         gw.data_ptr<float>(), g);
+  launch(ch.kern, ch.blocks, 2 * ch.tile, (const bf16*)go.data_ptr(),
+         (const bf16*)x.data_ptr(), gw.data_ptr<float>(), g);
   return gw;
 }
 
-static void launch_pw(const torch::Tensor& x, const torch::Tensor& w,
-                      const float* bias, torch::Tensor& out, PwGeom g) {
-  using Kern = void (*)(const bf16*, const bf16*, const float*, bf16*, PwGeom);
-  static const Kern skinny[2][3] = {
+// The 1x1 GEMM kernel and block tile of a launch: the only place that
+// decides them. C is the reduction dim, K the output channels.
+struct PwChoice {
+  void (*kern)(const bf16*, const bf16*, const float*, bf16*, PwGeom);
+  int bm, bn;  // block tile: output channels x pixels
+  std::string label;
+};
+
+static PwChoice choose_pw(int C, int K, int64_t OHW, int sw, int osw) {
+  static const decltype(PwChoice::kern) skinny[2][3] = {
       {pw_kernel<1, 1>, pw_kernel<2, 1>, pw_kernel<4, 1>},
       {pw_kernel<1, 2>, pw_kernel<2, 2>, pw_kernel<4, 2>}};
-  const int K = g.K, OHW = g.OH * g.OW;
-  const bool dense1 = g.sw == 1 && g.osw == 1;
-  Kern kern;
-  int bm, bn;  // block tile: output channels x pixels
-  if (dense1 && g.C >= 512 && K >= 256 && OHW % 256 == 0 &&
+  const bool dense1 = sw == 1 && osw == 1;
+  // read per call, so a change inside the process is seen
+  if (dense1 && C >= 512 && K >= 256 && OHW % 256 == 0 &&
       [] { const char* e = getenv("MPI4DL_PW_FAT256");
            return !(e && e[0] == '0'); }()) {
     // biggest fat shapes: 256x256 tile (2x MFMA per staged byte)
-    kern = pw_fat_kernel<8>;
-    bm = bn = 256;
-  } else if (dense1 && g.C >= 256 && K >= 128) {
+    return {pw_fat_kernel<8>, 256, 256, "pw_fat256"};
+  }
+  if (dense1 && C >= 256 && K >= 128) {
     // fat shapes (compute-bound): 128x128xBK64 dual-glds kernel.
     // measured: 2-buffer + 2 blocks/CU beats a 3-buffer span pipeline
     // ~2x here (the span lever only pays in the 1-block/CU VGPR~250
     // regime — guide §5 glds table)
-    kern = pw_fat_kernel<4>;
-    bm = bn = 128;
-  } else {
-    // measured: MFRAG=8 (BM=256, acc 128 f32/lane) LOSES ~1.4x on the
-    // skinny shapes — register pressure halves occupancy and these
-    // few-kstep kernels live on cross-block latency hiding. Keep BM<=128.
-    const int mi = (K <= 32) ? 0 : (K <= 64) ? 1 : 2;
-    kern = skinny[g.sw != 1][mi];
-    bm = 32 << mi;
-    bn = PW_BN;
+    return {pw_fat_kernel<4>, 128, 128, "pw_fat"};
   }
-  launch(kern, (int64_t)g.N * (OHW / bn) * ((K + bm - 1) / bm), 2 * bn,
-         (const bf16*)x.data_ptr(), (const bf16*)w.data_ptr(), bias,
-         (bf16*)out.data_ptr(), g);
+  // measured: MFRAG=8 (BM=256, acc 128 f32/lane) LOSES ~1.4x on the
+  // skinny shapes — register pressure halves occupancy and these
+  // few-kstep kernels live on cross-block latency hiding. Keep BM<=128.
+  const int mi = (K <= 32) ? 0 : (K <= 64) ? 1 : 2;
+  return {skinny[sw != 1][mi], 32 << mi, PW_BN,
+          "pw<" + std::to_string(1 << mi) + "," + std::to_string(sw) + ">" +
+              (osw != 1 ? ":scatter" : "")};
+}
+
+std::string pw_kernel_name(int64_t C, int64_t K, int64_t OHW, int64_t sw,
+                           int64_t osw) {
+  return choose_pw((int)C, (int)K, OHW, (int)sw, (int)osw).label;
+}
+
+static void launch_pw(const torch::Tensor& x, const torch::Tensor& w,
+                      const float* bias, torch::Tensor& out, PwGeom g) {
+  const int OHW = g.OH * g.OW;
+  const PwChoice ch = choose_pw(g.C, g.K, OHW, g.sw, g.osw);
+  launch(ch.kern,
+         (int64_t)g.N * (OHW / ch.bn) * ((g.K + ch.bm - 1) / ch.bm),
+         2 * ch.bn, (const bf16*)x.data_ptr(), (const bf16*)w.data_ptr(),
+         bias, (bf16*)out.data_ptr(), g);
 }
 
 // forward: x [N,C,H,W] bf16, w [K,C,1,1] bf16, stride (sh,sw), pad 0
@@ -768,4 +805,11 @@ void register_conv_pw(pybind11::module_& m) {
         "1x1 strided conv backward-data (scatter epilogue)");
   m.def("pw_bwdw", &conv_pw::pw_bwdw,
         "1x1 stride-1 conv backward-weight (NT MFMA GEMM, fp32 out)");
+  // what the launchers above pick, from plain integers: no tensor, no
+  // HIP call
+  m.def("pw_kernel_name", &conv_pw::pw_kernel_name,
+        "label of the kernel a 1x1 GEMM launch picks for (C, K, OHW, sw, "
+        "osw); C is the reduction dim, K the output channels");
+  m.def("pw_bwdw_kernel_name", &conv_pw::pw_bwdw_kernel_name,
+        "label of the kernel pw_bwdw launches for (N, K, C, OHW)");
 }

@@ -5,8 +5,10 @@ Shared by ``test_conv_oracle.py`` (CPU: the oracle checks itself) and
 
 * ``Case`` / ``CASES``: the shape matrix, each case labelled with the
   kernels it must reach.
-* ``expected_path``: the host-side dispatch, transcribed into Python, so
-  a CPU test can prove that each label is what the dispatch would pick.
+* ``expected_path``: what production code picks for a case, asked of
+  ``conv_native.conv_plan`` and of the built extension's name functions;
+  the labels in ``CASES`` are the hand-written expectation it is
+  compared with. No GPU is needed, but the extension must be built.
 * ``reference``: float64 on the CPU from the bf16-rounded inputs. It
   never touches MIOpen or hipBLASLt.
 * ``bound`` / ``assert_within``: a derived per-element error bound.
@@ -28,7 +30,6 @@ the bound is 0: structural zeros must be exact zeros.
 from __future__ import annotations
 
 import functools
-import os
 import zlib
 from dataclasses import dataclass
 
@@ -112,108 +113,69 @@ def leg_is_bf16(leg):
 
 
 # ---------------------------------------------------------------------------
-# Host-side dispatch, transcribed. References are to the sources as of
-# this file's commit:
-#   conv_fwd        mpi4dl_amd/csrc/conv_mfma.hip:694-725 (v2 predicate,
-#                   mfrag, the S*10+mfrag switch)
-#   launch_pw       mpi4dl_amd/csrc/conv_pw.hip:661-696 (fat256, fat,
-#                   skinny mfrag, stride template)
-#   pw_bwdw         mpi4dl_amd/csrc/conv_pw.hip:641-647 (`big`, slab loop)
-#   ConvFn          mpi4dl_amd/ops/conv_native.py:58-173
-#   _pw_geom_ok     mpi4dl_amd/ops/conv_native.py:41-53
+# What production code picks. Nothing of the dispatch is written here:
+# ``conv_native.conv_plan`` says which route each leg takes and with which
+# problem, and the extension's name functions, which call the choosers the
+# launchers call, say which kernel a native route then launches. This
+# file only spells the labels.
 # ---------------------------------------------------------------------------
 
 def _mfrag(K):
+    """Spells the MFRAG of a label in ``_build_cases``; decides nothing."""
     return 1 if K <= 32 else 2 if K <= 64 else 4
 
 
-def conv_fwd_path(C, K, H, W, R, S, sh, sw, ph, pw):
-    OH = (H + 2 * ph - R) // sh + 1
-    OW = (W + 2 * pw - S) // sw + 1
-    if (sh == 1 and sw == 1 and S in (1, 3, 7) and C * S >= 32
-            and (OH * OW) % 128 == 0 and OW % 8 == 0):
-        return f"v2<{S},{_mfrag(K)}>"
-    return "v1"
+def extension():
+    """The built extension. It cross-compiles and imports without a GPU;
+    ImportError if the tree is not built."""
+    from mpi4dl_amd import _gemscore
+    return _gemscore
 
 
-def launch_pw_path(C, K, OHW, sw, osw):
-    """C is the reduction dim and K the output channels of the launch."""
-    fat256_on = os.environ.get("MPI4DL_PW_FAT256", "1")[:1] != "0"
-    if (sw == 1 and osw == 1 and C >= 512 and K >= 256 and OHW % 256 == 0
-            and fat256_on):
-        return "pw_fat256"
-    if sw == 1 and osw == 1 and C >= 256 and K >= 128:
-        return "pw_fat"
-    return f"pw<{_mfrag(K)},{sw}>" + (":scatter" if osw != 1 else "")
+def leg_label(which, leg, ge):
+    """The label of one leg of a plan ('y', 'gx' or 'gw')."""
+    route, problem = leg
+    if route == "matmul":
+        return {"y": "blaslt:fwd", "gx": "blaslt:gx"}[which]
+    if route == "bmm":
+        return "blaslt:gw_bmm"
+    if route in ("pw_fwd", "pw_bwd_data_strided"):
+        return ge.pw_kernel_name(*problem)
+    if route == "pw_bwdw":
+        return ge.pw_bwdw_kernel_name(*problem)
+    if route == "pw_bwdw_sub":
+        return "sub:" + ge.pw_bwdw_kernel_name(*problem)
+    if route == "conv_fwd":
+        return ge.conv_fwd_kernel_name(*problem)
+    if route == "conv_fwd_zs":
+        return "zs:" + ge.conv_fwd_kernel_name(*problem)
+    assert route == "conv_bwd_weight", route
+    return "conv_bwdw"
 
 
-def pw_bwdw_path(N, K, C, OHW):
-    big = K >= 256 and C >= 256 and OHW >= 16384
-    tile = 256 if big else 128
-    mn = -(-K // tile) * -(-C // tile)
-    slab = OHW
-    while (slab > 512 and mn * N * (OHW // slab) < 384 and slab % 2 == 0
-           and (slab // 2) % 64 == 0):
-        slab //= 2
-    return f"pw_bwdw{tile}" + (":slab" if slab < OHW else "")
-
-
-def _pw_geom_ok(H, W, sh, sw):
-    oh = (H - 1) // sh + 1
-    ow = (W - 1) // sw + 1
-    if (oh * ow) % 128 != 0:
-        return False
-    if (sh, sw) != (1, 1):
-        return sh == 2 and sw == 2 and H % 2 == 0 and W % 2 == 0 and ow % 8 == 0
-    return True
-
-
-def _convfn_paths(c):
-    """ConvFn.forward/backward, leg by leg: y, gx, gw."""
-    s1 = (c.sh, c.sw) == (1, 1)
-    is_pw = (c.R == 1 and c.S == 1 and c.ph == 0 and c.pw == 0
-             and _pw_geom_ok(c.H, c.W, c.sh, c.sw))
+def expected_path(c, ge=None):
+    """The kernels production code picks for a case: for a direct entry,
+    its binding's name function on the arguments ``_run_gpu`` passes; for
+    autograd, the three legs of ``conv_plan``."""
+    ge = ge or extension()
     ohw = c.OH * c.OW
-    if is_pw and s1:
-        y = ("blaslt:fwd" if c.blaslt and c.K > 64
-             else launch_pw_path(c.C, c.K, ohw, 1, 1))
-        gx = ("blaslt:gx" if c.blaslt and c.C > 64
-              else launch_pw_path(c.K, c.C, ohw, 1, 1))
-        gw = ("blaslt:gw_bmm"
-              if c.blaslt and c.C * c.K >= 350_000 and ohw <= 32_768
-              else pw_bwdw_path(c.N, c.K, c.C, ohw))
-    elif is_pw:
-        y = launch_pw_path(c.C, c.K, ohw, c.sw, 1)
-        gx = launch_pw_path(c.K, c.C, ohw, 1, c.sw)
-        gw = "sub:" + pw_bwdw_path(c.N, c.K, c.C, ohw)
-    else:
-        y = conv_fwd_path(c.C, c.K, c.H, c.W, c.R, c.S, c.sh, c.sw, c.ph, c.pw)
-        if s1:
-            gx = conv_fwd_path(c.K, c.C, c.OH, c.OW, c.R, c.S, 1, 1,
-                               c.R - 1 - c.ph, c.S - 1 - c.pw)
-        else:
-            hs = (c.OH - 1) * c.sh + 1 + (c.H + 2 * c.ph - c.R) % c.sh
-            ws = (c.OW - 1) * c.sw + 1 + (c.W + 2 * c.pw - c.S) % c.sw
-            gx = "zs:" + conv_fwd_path(c.K, c.C, hs, ws, c.R, c.S, 1, 1,
-                                       c.R - 1 - c.ph, c.S - 1 - c.pw)
-        gw = "conv_bwdw"
-    return y, gx, gw
-
-
-def expected_path(c):
     if c.entry == "conv_fwd":
-        return conv_fwd_path(c.C, c.K, c.H, c.W, c.R, c.S, c.sh, c.sw,
-                             c.ph, c.pw)
+        return ge.conv_fwd_kernel_name(c.C, c.K, c.H, c.W, c.R, c.S, c.sh,
+                                       c.sw, c.ph, c.pw)
     if c.entry == "conv_bwd_weight":
         return "conv_bwdw"
     if c.entry == "pw_fwd":
-        return launch_pw_path(c.C, c.K, c.OH * c.OW, c.sw, 1)
+        return ge.pw_kernel_name(c.C, c.K, ohw, c.sw, 1)
     if c.entry == "pw_bwd_data_strided":
-        return launch_pw_path(c.K, c.C, c.OH * c.OW, 1, c.sw)
+        return ge.pw_kernel_name(c.K, c.C, ohw, 1, c.sw)
     if c.entry == "pw_bwdw":
-        return pw_bwdw_path(c.N, c.K, c.C, c.OH * c.OW)
+        return ge.pw_bwdw_kernel_name(c.N, c.K, c.C, ohw)
     assert c.entry == "autograd", c.entry
-    return "+".join(_convfn_paths(c))
+    from mpi4dl_amd.ops.conv_native import conv_plan
+    plan = conv_plan(c.N, c.C, c.K, c.H, c.W, c.R, c.S, c.sh, c.sw, c.ph,
+                     c.pw, blaslt=c.blaslt)
+    return "+".join(leg_label(which, leg, ge)
+                    for which, leg in zip(("y", "gx", "gw"), plan))
 
 
 # Every kernel instantiation and wrapper branch the matrix reaches. The
@@ -575,8 +537,9 @@ def check_case(case, results, what=""):
 
 class _Recorder:
     """Stands in for the extension module and notes, for every native
-    convolution binding called, the kernel that the call's own
-    arguments make the host code pick."""
+    convolution binding called, the kernel the extension names for the
+    shapes of that call's own arguments and result: the name functions
+    run the choosers the launch itself ran."""
 
     def __init__(self, ge):
         self._ge = ge
@@ -589,34 +552,29 @@ class _Recorder:
             return fn
 
         def wrapped(*args):
-            self.kernels.append(label(*args))
-            return fn(*args)
+            out = fn(*args)
+            self.kernels.append(label(out, *args))
+            return out
         return wrapped
 
-    @staticmethod
-    def _label_conv_fwd(x, w, bias, sh, sw, ph, pw):
+    def _label_conv_fwd(self, y, x, w, bias, sh, sw, ph, pw):
         (_, C, H, W), (K, _, R, S) = x.shape, w.shape
-        return conv_fwd_path(C, K, H, W, R, S, sh, sw, ph, pw)
+        return self._ge.conv_fwd_kernel_name(C, K, H, W, R, S, sh, sw, ph, pw)
 
-    @staticmethod
-    def _label_conv_bwd_weight(go, x, R, S, sh, sw, ph, pw):
+    def _label_conv_bwd_weight(self, gw, go, x, R, S, sh, sw, ph, pw):
         return "conv_bwdw"
 
-    @staticmethod
-    def _label_pw_fwd(x, w, bias, sh, sw):
-        (_, C, H, W), K = x.shape, w.shape[0]
-        ohw = ((H - 1) // sh + 1) * ((W - 1) // sw + 1)
-        return launch_pw_path(C, K, ohw, sw, 1)
+    def _label_pw_fwd(self, y, x, w, bias, sh, sw):
+        (_, K, OH, OW), C = y.shape, x.shape[1]
+        return self._ge.pw_kernel_name(C, K, OH * OW, sw, 1)
 
-    @staticmethod
-    def _label_pw_bwd_data_strided(go, wt, H, W, sh, sw):
+    def _label_pw_bwd_data_strided(self, gx, go, wt, H, W, sh, sw):
         (_, Kred, OH, OW), Cout = go.shape, wt.shape[0]
-        return launch_pw_path(Kred, Cout, OH * OW, 1, sw)
+        return self._ge.pw_kernel_name(Kred, Cout, OH * OW, 1, sw)
 
-    @staticmethod
-    def _label_pw_bwdw(go, x):
+    def _label_pw_bwdw(self, gw, go, x):
         (N, K, OH, OW), C = go.shape, x.shape[1]
-        return pw_bwdw_path(N, K, C, OH * OW)
+        return self._ge.pw_bwdw_kernel_name(N, K, C, OH * OW)
 
 
 def run_gpu(case, kernels=None):

@@ -3,8 +3,11 @@
 One test per case of ``conv_oracle.CASES``: the entry point runs once on
 the GPU, the results go to the CPU, and every element of every leg must
 lie within the derived bound of the float64 reference (``conv_oracle``'s
-docstring has the bound). ``test_conv_oracle.py`` proves on the CPU that
-each case's label is the kernel the dispatch picks.
+docstring has the bound). Each case's label must be what production code
+picks (``conv_oracle.expected_path`` asks ``conv_plan`` and the
+extension's kernel-name functions), and a recorder around the extension
+asks the same name functions about every binding call that really
+happens. ``test_conv_oracle.py`` checks the labels without a GPU.
 """
 
 import pytest
@@ -20,8 +23,7 @@ requires_gpu = pytest.mark.skipif(
 
 def _env(monkeypatch, case):
     monkeypatch.setenv("MPI4DL_PW_BLASLT", "1" if case.blaslt else "0")
-    for var in ("MPI4DL_PW_FAT256", "MPI4DL_NATIVE_BWD_S2"):
-        monkeypatch.delenv(var, raising=False)
+    monkeypatch.delenv("MPI4DL_PW_FAT256", raising=False)
 
 
 @gpu
@@ -30,11 +32,12 @@ def _env(monkeypatch, case):
 def test_conv_exact(cid, monkeypatch):
     case = co.CASE_BY_ID[cid]
     _env(monkeypatch, case)
+    assert co.expected_path(case) == case.path
     kernels = []
     results = co.run_gpu(case, kernels)
-    # the bindings that ran, judged by their own arguments, are the ones
-    # the label names (ConvFn.backward computes gw before gx; the
-    # hipBLASLt branches call no binding)
+    # the bindings that ran, named by the extension from their own
+    # arguments, are the ones the label names (ConvFn.backward computes
+    # gw before gx; the hipBLASLt branches call no binding)
     y, gx, gw = (case.path.split("+") + ["", ""])[:3]
     order = [y, gw, gx] if case.entry == "autograd" else [y]
     named = [k.split(":", 1)[-1] if k[:3] in ("zs:", "sub") else k
