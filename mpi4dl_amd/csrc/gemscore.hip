@@ -1559,15 +1559,14 @@ static inline bool aligned16(const void* p) {
 
 // Shape half of the fast-path predicate: 2-byte dtype, whole 16-byte
 // chunks on both sides, and (H, W) <-> (OH, OW) consistent with (k,s,p).
-static bool pool_vec_shape_ok(at::ScalarType st, int64_t H, int64_t W,
+static bool pool_vec_shape_ok(int64_t itemsize, int64_t H, int64_t W,
                               int64_t OH, int64_t OW, int64_t k, int64_t s,
                               int64_t p) {
   const bool geom = (k == 3 && s == 1 && p == 1) ||
                     (k == 3 && s == 2 && p == 1) ||
                     (k == 2 && s == 2 && p == 0);
   if (!geom) return false;
-  if (st != at::ScalarType::Half && st != at::ScalarType::BFloat16)
-    return false;
+  if (itemsize != 2) return false;  // Half and BFloat16
   if (H < 1 || W < 8 || OH < 1 || OW < 8 || W % 8 != 0 || OW % 8 != 0)
     return false;
   if (OH != (H + 2 * p - k) / s + 1 || OW != (W + 2 * p - k) / s + 1)
@@ -1654,11 +1653,99 @@ void avgpool_bwd_vec(const T* go, T* gi, int64_t NC, int H, int W, int64_t gr0,
   }
 }
 
+// ---------------- pool kernel choice ----------------
+// One chooser for the four bindings and for pool_kernel_name: the label
+// is spelt from the same (vec, kk, ss) the launch switches on.
+
+enum class PoolOp { MaxFwd, MaxBwd, AvgFwd, AvgBwd };
+
+struct PoolChoice {
+  bool vec;   // a *_vec kernel for (kk, ss); else <kk, ss> of the generic one
+  int kk, ss; // generic: the template arguments, <0,0> = runtime (k, s)
+  std::string label;
+};
+
+static inline int64_t pool_out(int64_t n, int64_t k, int64_t s, int64_t p) {
+  return (n + 2 * p - k) / s + 1;
+}
+
+// `aligned`: the tensors are non-empty and every base pointer of the
+// launch is 16-byte aligned. `go_bs`: batch stride of go in elements for
+// the backward ops (0 = contiguous).
+static PoolChoice choose_pool(PoolOp op, int64_t itemsize, int64_t H,
+                              int64_t W, int64_t k, int64_t s, int64_t p,
+                              bool aligned, int64_t go_bs,
+                              bool force_generic) {
+  const bool is_max = op == PoolOp::MaxFwd || op == PoolOp::MaxBwd;
+  const bool is_bwd = op == PoolOp::MaxBwd || op == PoolOp::AvgBwd;
+  const bool vec =
+      !force_generic && aligned && (is_max || (k == 3 && s == 1)) &&
+      pool_vec_shape_ok(itemsize, H, W, pool_out(H, k, s, p),
+                        pool_out(W, k, s, p), k, s, p) &&
+      (!is_bwd || go_bs % 8 == 0);
+  PoolChoice c{vec, (int)k, (int)s, ""};
+  const std::string dir = is_bwd ? "_bwd" : "_fwd";
+  if (vec) {
+    if (!is_max)
+      c.label = "vec:avg3s1" + dir;
+    else if (k == 3 && !is_bwd)
+      c.label = "vec:max3_fwd<" + std::to_string(c.ss) + ">";
+    else
+      c.label = "vec:max" + std::to_string(c.kk) + "s" + std::to_string(c.ss) +
+                dir;
+    return c;
+  }
+  const bool spec = (k == 3 && (s == 1 || s == 2)) ||
+                    (is_max && k == 2 && s == 2);
+  if (!spec) c.kk = c.ss = 0;
+  c.label = std::string(is_max ? "max" : "avg") + dir + "<" +
+            std::to_string(c.kk) + "," + std::to_string(c.ss) + ">";
+  return c;
+}
+
+// Geometry every pool binding needs before it sizes anything.
+static void check_pool_geom(const char* who, int64_t H, int64_t W, int64_t k,
+                            int64_t s, int64_t p) {
+  TORCH_CHECK(k >= 1, who, ": kernel size must be >= 1, got k=", k);
+  TORCH_CHECK(s >= 1, who, ": stride must be >= 1, got s=", s);
+  TORCH_CHECK(p >= 0, who, ": padding must be >= 0, got p=", p);
+  TORCH_CHECK(2 * p <= k, who, ": padding must be at most half the kernel, "
+              "got p=", p, " k=", k);
+  TORCH_CHECK(H + 2 * p >= k && W + 2 * p >= k, who, ": kernel larger than "
+              "the padded input, got H=", H, " W=", W, " k=", k, " p=", p);
+}
+
+static void check_pool_out(const char* who, const torch::Tensor& t,
+                           const char* what, int64_t H, int64_t W, int64_t k,
+                           int64_t s, int64_t p) {
+  TORCH_CHECK(t.dim() == 4, who, ": ", what, " must be 4-D");
+  const int64_t OH = pool_out(H, k, s, p), OW = pool_out(W, k, s, p);
+  TORCH_CHECK(t.size(2) == OH && t.size(3) == OW, who, ": ", what, " is ",
+              t.size(2), "x", t.size(3), " but (H, W, k, s, p) give ", OH, "x",
+              OW);
+}
+
+std::string pool_kernel_name(const std::string& op, int64_t itemsize, int64_t H,
+                             int64_t W, int64_t k, int64_t s, int64_t p,
+                             bool aligned, int64_t go_bs) {
+  check_pool_geom("pool_kernel_name", H, W, k, s, p);
+  PoolOp o;
+  if (op == "max_fwd") o = PoolOp::MaxFwd;
+  else if (op == "max_bwd") o = PoolOp::MaxBwd;
+  else if (op == "avg_fwd") o = PoolOp::AvgFwd;
+  else if (op == "avg_bwd") o = PoolOp::AvgBwd;
+  else TORCH_CHECK(false, "pool_kernel_name: op must be max_fwd, max_bwd, "
+                   "avg_fwd or avg_bwd, got ", op);
+  return choose_pool(o, itemsize, H, W, k, s, p, aligned, go_bs, false).label;
+}
+
 std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k, int64_t s,
                                        int64_t p, bool force_generic) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
+  TORCH_CHECK(x.dim() == 4, "maxpool_fwd: x must be 4-D");
+  check_pool_geom("maxpool_fwd", x.size(2), x.size(3), k, s, p);
   TORCH_CHECK(k * k <= 256,
               "maxpool_fwd: k*k must fit the u8 window index, got k=", k);
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
   const int64_t N = x.size(0), C = x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
   const int OH = (H + 2 * (int)p - (int)k) / (int)s + 1;
@@ -1667,18 +1754,19 @@ std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k, int64_t s,
   auto idx = torch::empty({N, C, OH, OW}, x.options().dtype(torch::kByte));
   const int64_t total = N * C * (int64_t)OH * OW;
   auto stream = at::cuda::getCurrentCUDAStream();
-  const bool fast = !force_generic && total > 0 &&
-                    pool_vec_shape_ok(x.scalar_type(), H, W, OH, OW, k, s, p) &&
-                    aligned16(x.data_ptr()) && aligned16(y.data_ptr()) &&
-                    aligned16(idx.data_ptr());
+  const PoolChoice ch = choose_pool(
+      PoolOp::MaxFwd, x.element_size(), H, W, k, s, p,
+      total > 0 && aligned16(x.data_ptr()) && aligned16(y.data_ptr()) &&
+          aligned16(idx.data_ptr()),
+      0, force_generic);
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
       "maxpool_fwd", [&] {
-        if (fast) {
+        if (ch.vec) {
           maxpool_fwd_vec<scalar_t>(x.data_ptr<scalar_t>(),
                                     y.data_ptr<scalar_t>(),
                                     idx.data_ptr<uint8_t>(), N * C, H, W, OH, OW,
-                                    (int)k, (int)s, stream.stream());
+                                    ch.kk, ch.ss, stream.stream());
           return;
         }
         auto launch = [&](auto kernel) {
@@ -1687,14 +1775,16 @@ std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k, int64_t s,
                              y.data_ptr<scalar_t>(), idx.data_ptr<uint8_t>(),
                              N * C, H, W, OH, OW, (int)k, (int)s, (int)p);
         };
-        if (k == 3 && s == 2)
+        if (ch.kk == 3 && ch.ss == 2)
           launch(maxpool_fwd_kernel<scalar_t, 3, 2>);
-        else if (k == 3 && s == 1)
+        else if (ch.kk == 3 && ch.ss == 1)
           launch(maxpool_fwd_kernel<scalar_t, 3, 1>);
-        else if (k == 2 && s == 2)
+        else if (ch.kk == 2 && ch.ss == 2)
           launch(maxpool_fwd_kernel<scalar_t, 2, 2>);
-        else
+        else if (ch.kk == 0)
           launch(maxpool_fwd_kernel<scalar_t, 0, 0>);
+        else
+          TORCH_CHECK(false, "maxpool_fwd: no kernel for ", ch.label);
       });
   return {y, idx};
 }
@@ -1702,12 +1792,17 @@ std::vector<torch::Tensor> maxpool_fwd(torch::Tensor x, int64_t k, int64_t s,
 torch::Tensor maxpool_bwd(torch::Tensor go, torch::Tensor idx, int64_t H,
                           int64_t W, int64_t k, int64_t s, int64_t p,
                           bool force_generic) {
-  const bool go_contig = go.dim() == 4 && go.is_contiguous();
+  check_pool_geom("maxpool_bwd", H, W, k, s, p);
+  check_pool_out("maxpool_bwd", go, "go", H, W, k, s, p);
+  check_pool_out("maxpool_bwd", idx, "idx", H, W, k, s, p);
+  TORCH_CHECK(idx.size(0) == go.size(0) && idx.size(1) == go.size(1),
+              "maxpool_bwd: idx and go disagree on (N, C)");
+  TORCH_CHECK(k * k <= 256,
+              "maxpool_bwd: k*k must fit the u8 window index, got k=", k);
+  const bool go_contig = go.is_contiguous();
   TORCH_CHECK(go.is_cuda() && (go_contig || go_plane_dense(go)),
               "maxpool_bwd: go must be a channel slice of a contiguous NCHW "
               "tensor");
-  TORCH_CHECK(k * k <= 256,
-              "maxpool_bwd: k*k must fit the u8 window index, got k=", k);
   TORCH_CHECK(idx.is_cuda() && idx.is_contiguous() &&
               idx.scalar_type() == torch::kByte && idx.numel() == go.numel());
   const int64_t N = go.size(0), C = go.size(1);
@@ -1716,18 +1811,19 @@ torch::Tensor maxpool_bwd(torch::Tensor go, torch::Tensor idx, int64_t H,
   auto gi = torch::empty({N, C, H, W}, go.options());
   const int64_t total = N * C * H * W;
   auto stream = at::cuda::getCurrentCUDAStream();
-  const bool fast = !force_generic && total > 0 && go.numel() > 0 &&
-                    pool_vec_shape_ok(go.scalar_type(), H, W, OH, OW, k, s, p) &&
-                    go_bs % 8 == 0 && aligned16(go.data_ptr()) &&
-                    aligned16(idx.data_ptr()) && aligned16(gi.data_ptr());
+  const PoolChoice ch = choose_pool(
+      PoolOp::MaxBwd, go.element_size(), H, W, k, s, p,
+      total > 0 && go.numel() > 0 && aligned16(go.data_ptr()) &&
+          aligned16(idx.data_ptr()) && aligned16(gi.data_ptr()),
+      go_bs, force_generic);
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, go.scalar_type(),
       "maxpool_bwd", [&] {
-        if (fast) {
+        if (ch.vec) {
           maxpool_bwd_vec<scalar_t>(go.data_ptr<scalar_t>(),
                                     idx.data_ptr<uint8_t>(),
                                     gi.data_ptr<scalar_t>(), N * C, (int)H,
-                                    (int)W, OH, OW, (int)k, (int)s, C, go_bs,
+                                    (int)W, OH, OW, ch.kk, ch.ss, C, go_bs,
                                     stream.stream());
           return;
         }
@@ -1738,14 +1834,16 @@ torch::Tensor maxpool_bwd(torch::Tensor go, torch::Tensor idx, int64_t H,
                              N * C, (int)H, (int)W, OH, OW, (int)k, (int)s,
                              (int)p, C, go_bs);
         };
-        if (k == 3 && s == 1)
+        if (ch.kk == 3 && ch.ss == 1)
           launch(maxpool_bwd_kernel<scalar_t, 3, 1>);
-        else if (k == 3 && s == 2)
+        else if (ch.kk == 3 && ch.ss == 2)
           launch(maxpool_bwd_kernel<scalar_t, 3, 2>);
-        else if (k == 2 && s == 2)
+        else if (ch.kk == 2 && ch.ss == 2)
           launch(maxpool_bwd_kernel<scalar_t, 2, 2>);
-        else
+        else if (ch.kk == 0)
           launch(maxpool_bwd_kernel<scalar_t, 0, 0>);
+        else
+          TORCH_CHECK(false, "maxpool_bwd: no kernel for ", ch.label);
       });
   return gi;
 }
@@ -1753,7 +1851,9 @@ torch::Tensor maxpool_bwd(torch::Tensor go, torch::Tensor idx, int64_t H,
 torch::Tensor avgpool_fwd(torch::Tensor x, int64_t k, int64_t s, int64_t p,
                           int64_t gr0, int64_t gc0, int64_t Hg, int64_t Wg,
                           bool include_pad, bool force_generic) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous());
+  TORCH_CHECK(x.dim() == 4, "avgpool_fwd: x must be 4-D");
+  check_pool_geom("avgpool_fwd", x.size(2), x.size(3), k, s, p);
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
   const int64_t N = x.size(0), C = x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
   const int OH = (H + 2 * (int)p - (int)k) / (int)s + 1;
@@ -1761,13 +1861,14 @@ torch::Tensor avgpool_fwd(torch::Tensor x, int64_t k, int64_t s, int64_t p,
   auto y = torch::empty({N, C, OH, OW}, x.options());
   const int64_t total = N * C * (int64_t)OH * OW;
   auto stream = at::cuda::getCurrentCUDAStream();
-  const bool fast = !force_generic && total > 0 && k == 3 && s == 1 &&
-                    pool_vec_shape_ok(x.scalar_type(), H, W, OH, OW, k, s, p) &&
-                    aligned16(x.data_ptr()) && aligned16(y.data_ptr());
+  const PoolChoice ch = choose_pool(
+      PoolOp::AvgFwd, x.element_size(), H, W, k, s, p,
+      total > 0 && aligned16(x.data_ptr()) && aligned16(y.data_ptr()), 0,
+      force_generic);
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, x.scalar_type(),
       "avgpool_fwd", [&] {
-        if (fast) {
+        if (ch.vec) {
           avgpool_fwd_vec<scalar_t>(x.data_ptr<scalar_t>(),
                                     y.data_ptr<scalar_t>(), N * C, H, W, gr0,
                                     gc0, Hg, Wg, include_pad, stream.stream());
@@ -1780,9 +1881,14 @@ torch::Tensor avgpool_fwd(torch::Tensor x, int64_t k, int64_t s, int64_t p,
                              (int)k, (int)s, (int)p, (long)gr0, (long)gc0,
                              (long)Hg, (long)Wg, include_pad ? 1 : 0);
         };
-        if (k == 3 && s == 2) launch(avgpool_fwd_kernel<scalar_t, 3, 2>);
-        else if (k == 3 && s == 1) launch(avgpool_fwd_kernel<scalar_t, 3, 1>);
-        else launch(avgpool_fwd_kernel<scalar_t, 0, 0>);
+        if (ch.kk == 3 && ch.ss == 2)
+          launch(avgpool_fwd_kernel<scalar_t, 3, 2>);
+        else if (ch.kk == 3 && ch.ss == 1)
+          launch(avgpool_fwd_kernel<scalar_t, 3, 1>);
+        else if (ch.kk == 0)
+          launch(avgpool_fwd_kernel<scalar_t, 0, 0>);
+        else
+          TORCH_CHECK(false, "avgpool_fwd: no kernel for ", ch.label);
       });
   return y;
 }
@@ -1791,7 +1897,9 @@ torch::Tensor avgpool_bwd(torch::Tensor go, int64_t H, int64_t W, int64_t k,
                           int64_t s, int64_t p, int64_t gr0, int64_t gc0,
                           int64_t Hg, int64_t Wg, bool include_pad,
                           bool force_generic) {
-  const bool go_contig = go.dim() == 4 && go.is_contiguous();
+  check_pool_geom("avgpool_bwd", H, W, k, s, p);
+  check_pool_out("avgpool_bwd", go, "go", H, W, k, s, p);
+  const bool go_contig = go.is_contiguous();
   TORCH_CHECK(go.is_cuda() && (go_contig || go_plane_dense(go)),
               "avgpool_bwd: go must be a channel slice of a contiguous NCHW "
               "tensor");
@@ -1801,15 +1909,15 @@ torch::Tensor avgpool_bwd(torch::Tensor go, int64_t H, int64_t W, int64_t k,
   auto gi = torch::empty({N, C, H, W}, go.options());
   const int64_t total = N * C * H * W;
   auto stream = at::cuda::getCurrentCUDAStream();
-  const bool fast = !force_generic && total > 0 && go.numel() > 0 && k == 3 &&
-                    s == 1 &&
-                    pool_vec_shape_ok(go.scalar_type(), H, W, OH, OW, k, s, p) &&
-                    go_bs % 8 == 0 && aligned16(go.data_ptr()) &&
-                    aligned16(gi.data_ptr());
+  const PoolChoice ch = choose_pool(
+      PoolOp::AvgBwd, go.element_size(), H, W, k, s, p,
+      total > 0 && go.numel() > 0 && aligned16(go.data_ptr()) &&
+          aligned16(gi.data_ptr()),
+      go_bs, force_generic);
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, go.scalar_type(),
       "avgpool_bwd", [&] {
-        if (fast) {
+        if (ch.vec) {
           avgpool_bwd_vec<scalar_t>(go.data_ptr<scalar_t>(),
                                     gi.data_ptr<scalar_t>(), N * C, (int)H,
                                     (int)W, gr0, gc0, Hg, Wg, include_pad, C,
@@ -1824,9 +1932,14 @@ torch::Tensor avgpool_bwd(torch::Tensor go, int64_t H, int64_t W, int64_t k,
                              (long)gc0, (long)Hg, (long)Wg,
                              include_pad ? 1 : 0, C, go_bs);
         };
-        if (k == 3 && s == 2) launch(avgpool_bwd_kernel<scalar_t, 3, 2>);
-        else if (k == 3 && s == 1) launch(avgpool_bwd_kernel<scalar_t, 3, 1>);
-        else launch(avgpool_bwd_kernel<scalar_t, 0, 0>);
+        if (ch.kk == 3 && ch.ss == 2)
+          launch(avgpool_bwd_kernel<scalar_t, 3, 2>);
+        else if (ch.kk == 3 && ch.ss == 1)
+          launch(avgpool_bwd_kernel<scalar_t, 3, 1>);
+        else if (ch.kk == 0)
+          launch(avgpool_bwd_kernel<scalar_t, 0, 0>);
+        else
+          TORCH_CHECK(false, "avgpool_bwd: no kernel for ", ch.label);
       });
   return gi;
 }
@@ -2146,6 +2259,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("s"), py::arg("p"), py::arg("gr0"),
         py::arg("gc0"), py::arg("Hg"), py::arg("Wg"), py::arg("include_pad"),
         py::arg("force_generic") = false);
+  m.def("pool_kernel_name", &pool_kernel_name, py::arg("op"),
+        py::arg("itemsize"), py::arg("H"), py::arg("W"), py::arg("k"),
+        py::arg("s"), py::arg("p"), py::arg("aligned") = true,
+        py::arg("go_bs") = 0,
+        "label of the kernel the pool binding `op` (max_fwd, max_bwd, "
+        "avg_fwd, avg_bwd) launches; plain integers, no HIP call");
   m.def("bn_stats64", &bn_stats64);
   m.def("bn_apply", &bn_apply);
   m.def("bn_bwd_stats", &bn_bwd_stats);

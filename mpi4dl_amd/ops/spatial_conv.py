@@ -291,6 +291,18 @@ class HaloPool2d(_SpatialBase):
         ccnt = (torch.clamp(cols + k, max=Wg) - torch.clamp(cols, min=0)).clamp(min=0)
         return (rcnt.view(-1, 1) * ccnt.view(1, -1)).to(torch.float32)
 
+    def _to_global_divisors(self, avg, H_loc, W_loc):
+        """Turn count_include_pad=True averages (already rounded to the
+        tensor's dtype) into count_include_pad=False ones: times k*k/div
+        in fp32, rounded back once. The factor is exactly 1.0 wherever the
+        window lies inside the global image, so those pixels keep their
+        single rounding bit for bit; only image-border pixels round twice."""
+        k = self.kernel_size
+        div = self._avg_divisors(
+            avg.shape[-2], avg.shape[-1], H_loc, W_loc, avg.device
+        )
+        return (avg * (float(k * k) / div)).to(avg.dtype)
+
     def forward(self, x):
         h = self.halo_len
         k, s = self.kernel_size, self.stride
@@ -361,11 +373,7 @@ class HaloPool2d(_SpatialBase):
             )
             if self.count_include_pad:
                 return out
-            sums = out * float(k * k)
-            div = self._avg_divisors(
-                sums.shape[-2], sums.shape[-1], H_loc, W_loc, sums.device
-            )
-            return sums / div
+            return self._to_global_divisors(out, H_loc, W_loc)
         if self.d2 and h > 0:
             xp = (
                 outer_pad_only(x, self.layout, self.tile, h, fill=fill)
@@ -397,10 +405,6 @@ class HaloPool2d(_SpatialBase):
             )
         if self.count_include_pad or h == 0 or x.is_meta:
             return F.avg_pool2d(xp, k, s, padding=0, count_include_pad=True)
-        sums = F.avg_pool2d(xp, k, s, padding=0, count_include_pad=True) * float(
-            k * k
+        return self._to_global_divisors(
+            F.avg_pool2d(xp, k, s, padding=0, count_include_pad=True), H_loc, W_loc
         )
-        div = self._avg_divisors(
-            sums.shape[-2], sums.shape[-1], H_loc, W_loc, sums.device
-        )
-        return sums / div

@@ -454,12 +454,16 @@ def case_data(case):
 # Bound and assertion
 # ---------------------------------------------------------------------------
 
-def bound(ref, A, L, out_is_bf16, extra=None):
+def bound(ref, A, L, out_is_bf16, extra=None, eps=None):
     """Per-element error bound (module docstring). ``extra`` is the
-    derived term of a branch that rounds more than once."""
+    derived term of a branch that rounds more than once. ``eps`` is the
+    unit roundoff of the output format where it is not told by
+    ``out_is_bf16`` (the pool oracle's fp16 legs)."""
+    if eps is None:
+        eps = U_BF16 if out_is_bf16 else 0.0
     bd = 2.0 * L * U_FP32 * A
-    if out_is_bf16:
-        bd = bd + U_BF16 * ref.abs()
+    if eps:
+        bd = bd + eps * ref.abs()
     if extra is not None:
         bd = bd + extra
     return bd
@@ -484,7 +488,8 @@ def extra_term(case, leg, ref, A, b):
     return None
 
 
-def assert_within(got, ref, A, L, out_is_bf16, extra=None, what=""):
+def assert_within(got, ref, A, L, out_is_bf16, extra=None, what="",
+                  eps=None):
     """Fail unless every element of ``got`` is finite and within the
     bound of ``ref``. Reports the worst index, err/bound there and the
     number of elements over the bound. Returns the largest err/bound."""
@@ -497,7 +502,7 @@ def assert_within(got, ref, A, L, out_is_bf16, extra=None, what=""):
         raise AssertionError(
             f"{what}: {bad.shape[0]} non-finite values, first at "
             f"{tuple(bad[0].tolist())}")
-    bd = bound(ref, A, L, out_is_bf16, extra)
+    bd = bound(ref, A, L, out_is_bf16, extra, eps)
     err = (got - ref).abs()
     over = err > bd
     # err/bound, with err > 0 at bound == 0 (a structural zero) as inf
