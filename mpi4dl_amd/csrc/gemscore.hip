@@ -1444,6 +1444,89 @@ __global__ void bn_bwd_apply_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// State fan backward (ops/fuse.py, state_fan): the gradient of a cell
+// state y that was handed to several consumers, some through relu(y).
+// One pass reads every consumer's gradient once and writes
+//
+//   m = select(r <= 0, 0, fold(rel[0], rel[1], ...))          r = relu(y)
+//   g = fold(raw[0], ..., raw[slot-1], m, raw[slot], ...)
+//
+// where fold is a LEFT fold whose every partial sum is rounded to T: that
+// is what a chain of torch adds on T tensors (autograd's accumulation of
+// one gradient after the other) produces, so g has the same bits as the
+// unfused chain when the caller passes the terms in the order autograd
+// would have met them.
+//
+// Every term is dense or a channel slice of a contiguous NCHW tensor:
+// dense planes and channels, its own batch stride. r and g are dense.
+// Grid: y = image, x walks the image's C*HW elements V at a time; V is a
+// 16-byte slot when HW is a multiple of it and every base is aligned,
+// else 1. Pointers and strides travel by value in the kernel arguments.
+// ---------------------------------------------------------------------------
+
+constexpr int FAN_MAX = 4;  // raw terms, and ReLU terms, at most
+
+struct FanTerms {
+  const void* raw[FAN_MAX];
+  const void* rel[FAN_MAX];
+  int64_t raw_bs[FAN_MAX];
+  int64_t rel_bs[FAN_MAX];
+};
+
+template <typename T, int V>
+struct alignas(sizeof(T) * V) FanPack {
+  T v[V];
+};
+
+template <typename T, int NRAW, int NREL, int V>
+__global__ void __launch_bounds__(256)
+    fan_bwd_kernel(const FanTerms t, const T* __restrict__ r,
+                   T* __restrict__ g, int64_t per_img, int slot) {
+  using acc_t = std::conditional_t<std::is_same<T, double>::value, double, float>;
+  using Pack = FanPack<T, V>;
+  const int64_t n = blockIdx.y;
+  const int64_t nv = per_img / V;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t iv = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; iv < nv;
+       iv += stride) {
+    const int64_t i = iv * V;
+    Pack raw[NRAW ? NRAW : 1], rel[NREL ? NREL : 1], rr, out;
+#pragma unroll
+    for (int k = 0; k < NRAW; ++k)
+      raw[k] = *(const Pack*)((const T*)t.raw[k] + n * t.raw_bs[k] + i);
+#pragma unroll
+    for (int k = 0; k < NREL; ++k)
+      rel[k] = *(const Pack*)((const T*)t.rel[k] + n * t.rel_bs[k] + i);
+    if (NREL) rr = *(const Pack*)(r + n * per_img + i);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      // a fold's first term enters as it is; a + b == b + a, so the masked
+      // sum in slot 0 may be added to raw[0] instead of the other way round
+      acc_t m = (acc_t)0;
+      if (NREL) {
+        m = (acc_t)rel[0].v[e];
+#pragma unroll
+        for (int k = 1; k < NREL; ++k)
+          m = (acc_t)(T)(m + (acc_t)rel[k].v[e]);
+        if ((acc_t)rr.v[e] <= (acc_t)0) m = (acc_t)0;
+      }
+      acc_t a = m;
+      if (NRAW) {
+        a = (acc_t)raw[0].v[e];
+        if (NREL && slot == 0) a = (acc_t)(T)(a + m);
+#pragma unroll
+        for (int k = 1; k <= NRAW; ++k) {
+          if (NREL && k == slot) a = (acc_t)(T)(a + m);
+          if (k < NRAW) a = (acc_t)(T)(a + (acc_t)raw[k].v[e]);
+        }
+      }
+      out.v[e] = (T)a;
+    }
+    *(Pack*)(g + n * per_img + i) = out;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Fused momentum-SGD on flat fp32 buffers: one kernel for the whole
 // model step (replaces ~3 torch launches per parameter — the profile
 // showed 5.8k tiny CUDAFunctor_add kernels per step).
@@ -2233,6 +2316,86 @@ torch::Tensor bn_bwd_apply_region(torch::Tensor go, torch::Tensor x,
                              (int)margin[2], (int)(W - margin[3]));
 }
 
+// ---------------- state fan binding ----------------
+
+// f(std::integral_constant<int, n>) for a run-time 0 <= n <= FAN_MAX
+template <int I = 0, typename F>
+static void with_count(int64_t n, F&& f) {
+  if constexpr (I > FAN_MAX) {
+    TORCH_CHECK(false, "fan_bwd: at most ", FAN_MAX, " terms of a kind");
+  } else {
+    if (n == I) f(std::integral_constant<int, I>{});
+    else with_count<I + 1>(n, f);
+  }
+}
+
+// g of fan_bwd_kernel. raw / rel: the gradients in fold order, each dense
+// or a channel slice (go_plane_dense); r = relu(y), dense, needed when rel
+// is not empty; slot = the number of raw terms folded before the masked sum.
+torch::Tensor fan_bwd(std::vector<torch::Tensor> raw,
+                      std::vector<torch::Tensor> rel,
+                      c10::optional<torch::Tensor> r, int64_t slot) {
+  const int64_t nraw = (int64_t)raw.size(), nrel = (int64_t)rel.size();
+  TORCH_CHECK(nraw + nrel >= 1, "fan_bwd: no terms");
+  TORCH_CHECK(nraw <= FAN_MAX && nrel <= FAN_MAX, "fan_bwd: at most ",
+              FAN_MAX, " raw and ", FAN_MAX, " ReLU terms");
+  TORCH_CHECK(slot >= 0 && slot <= nraw, "fan_bwd: slot outside the raw fold");
+  const torch::Tensor& first = nraw ? raw[0] : rel[0];
+  TORCH_CHECK(first.dim() == 4, "fan_bwd: terms are 4-D");
+  const int64_t N = first.size(0), C = first.size(1);
+  const int64_t HW = first.size(2) * first.size(3);
+  const int64_t per_img = C * HW;
+  const int64_t vec = 16 / (int64_t)first.element_size();
+  bool vec_ok = HW % vec == 0;
+  FanTerms t = {};
+  auto take = [&](const torch::Tensor& a, const void*& p, int64_t& bs) {
+    TORCH_CHECK(a.is_cuda() && a.sizes() == first.sizes() &&
+                    a.scalar_type() == first.scalar_type() &&
+                    a.get_device() == first.get_device() && go_plane_dense(a),
+                "fan_bwd: every term is a CUDA tensor of one shape and dtype, "
+                "dense or a channel slice of a contiguous tensor");
+    p = a.data_ptr();
+    bs = a.stride(0);
+    vec_ok = vec_ok && aligned16(p) && bs % vec == 0;
+  };
+  for (int64_t k = 0; k < nraw; ++k) take(raw[k], t.raw[k], t.raw_bs[k]);
+  for (int64_t k = 0; k < nrel; ++k) take(rel[k], t.rel[k], t.rel_bs[k]);
+  const void* rp = nullptr;
+  if (nrel) {
+    TORCH_CHECK(r.has_value() && r->is_cuda() && r->is_contiguous() &&
+                    r->sizes() == first.sizes() &&
+                    r->scalar_type() == first.scalar_type() &&
+                    r->get_device() == first.get_device(),
+                "fan_bwd: r must be contiguous with the terms' shape and dtype");
+    rp = r->data_ptr();
+    vec_ok = vec_ok && aligned16(rp);
+  }
+  auto g = torch::empty(first.sizes(), first.options());
+  if (g.numel() == 0) return g;
+  TORCH_CHECK(N <= 65535, "fan_bwd: batch too large for the grid");
+  vec_ok = vec_ok && aligned16(g.data_ptr());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  AT_DISPATCH_FLOATING_TYPES_AND2(
+      at::ScalarType::Half, at::ScalarType::BFloat16, first.scalar_type(),
+      "fan_bwd", [&] {
+        with_count(nraw, [&](auto nraw_c) {
+          with_count(nrel, [&](auto nrel_c) {
+            with_bool(vec_ok, [&](auto vec_c) {
+              constexpr int V =
+                  decltype(vec_c)::value ? 16 / (int)sizeof(scalar_t) : 1;
+              hipLaunchKernelGGL(
+                  (fan_bwd_kernel<scalar_t, decltype(nraw_c)::value,
+                                  decltype(nrel_c)::value, V>),
+                  dim3(grid_for(per_img / V, 256), (uint32_t)N), dim3(256), 0,
+                  stream.stream(), t, (const scalar_t*)rp,
+                  g.data_ptr<scalar_t>(), per_img, (int)slot);
+            });
+          });
+        });
+      });
+  return g;
+}
+
 }  // namespace
 
 void register_conv_mfma(pybind11::module_& m);
@@ -2281,5 +2444,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("y"), py::arg("mean"), py::arg("invstd"),
         py::arg("w"), py::arg("gsum"), py::arg("gxsum"), py::arg("n"),
         py::arg("relu"), py::arg("margin"));
+  m.def("fan_bwd", &fan_bwd, py::arg("raw"), py::arg("rel"), py::arg("r"),
+        py::arg("slot"),
+        "gradient of a fanned-out state: ordered fold of raw and ReLU-masked "
+        "consumer gradients (ops/fuse.py)");
+  m.attr("FAN_MAX") = (int)FAN_MAX;
   m.attr("gfx_arch") = "gfx950";
 }

@@ -102,7 +102,9 @@ class FactorizedReduce(nn.Module):
         self.bn = mknorm(cout)
 
     def forward(self, x):
-        x = self.relu(x)
+        return self.after_relu(self.relu(x))
+
+    def after_relu(self, x):
         x = torch.cat([self.conv1(x), self.conv2(x)], dim=1)
         return self.bn(x)
 
@@ -215,6 +217,25 @@ class Stem(nn.Module):
         return self.bn(self.conv(self.relu(x)))
 
 
+def _reduce(mod: nn.Module, t: Tensor, glue: bool) -> Tensor:
+    """A cell's input reduction. Its leading ReLU stays in the module (the
+    state-dict keys and indices do not move), but with the cell glue on the
+    ReLU'd input comes from ops/fuse.shared_relu: a cell output is
+    ReLU'd once for the two cells that read it, and its gradient is
+    formed in one pass."""
+    if not glue or isinstance(mod, nn.Identity):
+        return mod(t)
+    from ..ops.fuse import shared_relu
+
+    x = shared_relu(t)
+    if isinstance(mod, FactorizedReduce):
+        return mod.after_relu(x)
+    assert isinstance(mod[0], nn.ReLU)
+    for m in list(mod)[1:]:
+        x = m(x)
+    return x
+
+
 class Cell(nn.Module):
     """One AmoebaNet cell (reference Cell :449-533): takes (s1, s2) — or a
     single tensor used for both — reduces them to ``channels``, applies the
@@ -256,17 +277,63 @@ class Cell(nn.Module):
                 make_op(name, channels, stride, ctx, mknorm,
                         ref_quirks=ref_quirks)
             )
+        self._fans = self._fan_plan()
+
+    def _fan_plan(self):
+        """state index -> (kinds, where) for the states that go through
+        ops/fuse.state_fan: those with a ReLU consumer or several
+        consumers. ``kinds`` lists the consumers (True = through ReLU) in
+        the order in which forward() creates their autograd nodes, which
+        is not the order of the get() calls: an Identity op hands its
+        state on to the pair's sum, or to the final AddCat when the sum
+        lives only in the concat. ``where`` maps an op's position, or
+        "cat" for the state's own concat slice, to its place in kinds."""
+        late = float("inf")
+        cons = {}
+        for pos, idx in enumerate(self.indices):
+            if isinstance(self.operations[pos], nn.Identity):
+                sidx = 2 + pos // 2
+                # AddCat's backward sums a tensor's slices in concat order
+                when = (
+                    (late, -self.concat.index(sidx))
+                    if sidx in self._cat_only
+                    else ((pos | 1) + 0.5, 0)
+                )
+            else:
+                when = (pos, 0)
+            cons.setdefault(idx, []).append((when, pos, self.wants_relu[pos]))
+        for at, idx in enumerate(self.concat):
+            if idx not in self._cat_only:
+                cons.setdefault(idx, []).append(((late, -at), "cat", False))
+        plan = {}
+        for idx, cs in cons.items():
+            cs.sort(key=lambda c: c[0])
+            kinds = tuple(k for _, _, k in cs)
+            if len(kinds) > 1 or any(kinds):
+                plan[idx] = (kinds, {key: j for j, (_, key, _) in enumerate(cs)})
+        return plan
 
     def forward(self, input_or_states):
+        from ..ops.fuse import add_cat, glue_enabled, state_fan
+
         if isinstance(input_or_states, tuple):
             s1, s2 = input_or_states
         else:
             s1 = s2 = input_or_states
         skip = s1
-        states = [self.reduce1(s1), self.reduce2(s2)]
+        glue = glue_enabled()
+        states = [
+            _reduce(self.reduce1, s1, glue), _reduce(self.reduce2, s2, glue)
+        ]
         relu_cache = {}
+        fans = {}
 
-        def get(idx, want_relu):
+        def get(idx, key, want_relu):
+            if glue and idx in self._fans:
+                kinds, where = self._fans[idx]
+                if idx not in fans:
+                    fans[idx] = state_fan(states[idx], kinds)
+                return fans[idx][where[key]]
             if not want_relu:
                 return states[idx]
             if idx not in relu_cache:
@@ -275,9 +342,9 @@ class Cell(nn.Module):
 
         pending = {}
         for i in range(0, len(self.operations), 2):
-            h1 = self.operations[i](get(self.indices[i], self.wants_relu[i]))
+            h1 = self.operations[i](get(self.indices[i], i, self.wants_relu[i]))
             h2 = self.operations[i + 1](
-                get(self.indices[i + 1], self.wants_relu[i + 1])
+                get(self.indices[i + 1], i + 1, self.wants_relu[i + 1])
             )
             sidx = 2 + i // 2
             if sidx in self._cat_only:
@@ -285,10 +352,9 @@ class Cell(nn.Module):
                 states.append(None)
             else:
                 states.append(h1 + h2)
-        from ..ops.fuse import add_cat
 
         entries = [
-            pending[i] if i in pending else (states[i], None)
+            pending[i] if i in pending else (get(i, "cat", False), None)
             for i in self.concat
         ]
         return add_cat(entries), skip

@@ -190,6 +190,11 @@ class CellD2(nn.Module):
         else:
             s1 = s2 = input_or_states
         skip = s1
+        # amoebanet.Cell's fused glue (ops/fuse.py: state_fan, shared_relu)
+        # is not used here: get() below interleaves the ReLU with the fused
+        # halo exchange and its crops, so a state's consumers are not the
+        # plain aliases the fan hands out. This loop keeps a ReLU per
+        # reduction and autograd's own gradient sums.
         states = [self.reduce1(s1), self.reduce2(s2)]
         relu_cache = {}
         halo_cache = {}  # (state idx, h) -> exchanged tensor

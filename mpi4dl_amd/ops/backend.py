@@ -46,3 +46,10 @@ def ext():
 
 def available() -> bool:
     return _load() is not None
+
+
+def cell_glue_enabled() -> bool:
+    """MPI4DL_CELL_GLUE=0 restores the unfused cell glue in the same build:
+    torch.relu per consumer and autograd's pairwise gradient adds in the
+    cells (ops/fuse.py). A cell reads it once per forward."""
+    return os.environ.get("MPI4DL_CELL_GLUE", "1") != "0"

@@ -42,6 +42,19 @@ def _as_list(spec):
     return [tuple(spec)]
 
 
+def _unshared(cell):
+    """cell for a checkpoint: its forward and its recompute both run with
+    the cells' shared input ReLU off (ops/fuse.relu_sharing), so both save
+    the same tensors."""
+    from ..ops.fuse import relu_sharing
+
+    def run(x):
+        with relu_sharing(False):
+            return cell(x)
+
+    return run
+
+
 class train_model:
     """One pipeline-stage engine living on one rank/GPU.
 
@@ -192,7 +205,7 @@ class train_model:
         from torch.utils.checkpoint import checkpoint
 
         for cell in self.models:
-            x = checkpoint(cell, x, use_reentrant=False)
+            x = checkpoint(_unshared(cell), x, use_reentrant=False)
         return x
 
     def _leaf(self, b):
