@@ -31,7 +31,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from ..ops.halo import HaloExchanger, TileLayout, halo_pad_d2
+from ..ops.halo import exchanger_for, halo_pad_d2
 from ..ops.plan import SpatialPlan
 from .amoebanet import (
     _bn_relu,
@@ -61,12 +61,8 @@ def _surplus(ctx, h):
     """(top, bottom, left, right) surplus a halo-h fused exchange leaves
     on THIS tile (HaloExchanger.pads_d2 semantics: interior sides get the
     halo, image-boundary sides 0; a single tile has none)."""
-    if ctx is None or ctx["num_spatial_parts"] <= 1:
-        return (0, 0, 0, 0)
-    layout = TileLayout(ctx["num_spatial_parts"], ctx["slice_method"])
-    return HaloExchanger(
-        layout, ctx["spatial_local_rank"], ctx["rank_of_tile"]
-    ).pads_d2(h)
+    ex = exchanger_for(**ctx) if ctx is not None else None
+    return ex.pads_d2(h) if ex is not None else (0, 0, 0, 0)
 
 
 def _bn_margin(bn, margin):
@@ -176,13 +172,7 @@ class CellD2(nn.Module):
             )
 
         self.grad_mode = (ctx or {}).get("grad_mode", "exact")
-        if ctx is not None and ctx["num_spatial_parts"] > 1:
-            layout = TileLayout(ctx["num_spatial_parts"], ctx["slice_method"])
-            self.exchanger = HaloExchanger(
-                layout, ctx["spatial_local_rank"], ctx["rank_of_tile"]
-            )
-        else:
-            self.exchanger = None
+        self.exchanger = exchanger_for(**ctx) if ctx is not None else None
 
     def forward(self, input_or_states):
         if isinstance(input_or_states, tuple):
@@ -223,9 +213,7 @@ class CellD2(nn.Module):
                     )
                 et, have = halo_cache[key]
                 if have > need:
-                    tb, bb, lb, rb = self.exchanger.pads_d2(have - need)
-                    H, W = et.shape[-2], et.shape[-1]
-                    et = et[:, :, tb : H - bb, lb : W - rb]
+                    et = self.exchanger.crop_d2(et, have - need)
                 t = et
             return t
 

@@ -29,7 +29,7 @@ from typing import Optional
 
 import torch.nn as nn
 
-from ..ops.halo import halo_pad_d2
+from ..ops.halo import TileLayout, exchanger_for, halo_pad_d2
 from ..ops.plan import SpatialPlan
 from ..ops.spatial_conv import outer_pad_only
 from .resnet import Head
@@ -48,9 +48,7 @@ class CropInterior(nn.Module):
     def forward(self, x):
         if self.exchanger is None or self.n == 0:
             return x
-        t, b, l, r = self.exchanger.pads_d2(self.n)
-        H, W = x.shape[-2], x.shape[-1]
-        return x[:, :, t : H - b, l : W - r]
+        return self.exchanger.crop_d2(x, self.n)
 
 
 class BottleneckV2D2(nn.Module):
@@ -66,15 +64,9 @@ class BottleneckV2D2(nn.Module):
                  pre_h: int = 0):
         super().__init__()
         assert in_ch == out_ch, "D2 blocks are the no-projection blocks"
-        from ..ops.halo import HaloExchanger, TileLayout
-
         self.layout = TileLayout(ctx["num_spatial_parts"], ctx["slice_method"])
         self.tile = ctx["spatial_local_rank"]
-        self.exchanger = (
-            HaloExchanger(self.layout, self.tile, ctx["rank_of_tile"])
-            if ctx["num_spatial_parts"] > 1
-            else None
-        )
+        self.exchanger = exchanger_for(**ctx)
         self.grad_mode = ctx.get("grad_mode", "exact")
         self.pre_h = pre_h
         self.pre1 = nn.Sequential(mknorm(in_ch), nn.ReLU(inplace=True))

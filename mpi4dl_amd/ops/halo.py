@@ -126,6 +126,23 @@ def recv_region(d, H, W, h, off=None):
     return rs, cs
 
 
+@dataclass
+class _Strip:
+    """One neighbour's share of an exchange: what goes to ``peer`` and
+    what comes back. Boxes are (row, col, rows, cols)."""
+
+    peer: int
+    send_tag: int
+    send_box: Tuple[int, int, int, int]
+    recv_tag: int
+    recv_box: Tuple[int, int, int, int]
+
+
+def _box(x, box):
+    r, c, rows, cols = box
+    return x[:, :, r : r + rows, c : c + cols]
+
+
 class HaloExchanger:
     """Performs forward halo exchange and (optionally) the transposed
     backward exchange among the tile ranks of one spatial partition.
@@ -135,26 +152,14 @@ class HaloExchanger:
     reference spatial.py:913-918).
     """
 
-    def __init__(
-        self,
-        layout: TileLayout,
-        tile: int,
-        rank_of_tile,
-        side_stream: bool = True,
-    ):
+    def __init__(self, layout: TileLayout, tile: int, rank_of_tile):
         self.layout = layout
         self.tile = tile
         self.rank_of_tile = rank_of_tile
         self.neigh = layout.neighbours(tile)
-        self._stream = None
-        self.side_stream = side_stream
-
-    def stream(self):
-        if self._stream is None and torch.cuda.is_available() and self.side_stream:
-            self._stream = torch.cuda.Stream()
-        return self._stream
-
-    # -- forward -------------------------------------------------------------
+        # (shape, h, dtype, device, grad, off, nominal) -> strips, and on
+        # the GPU their descriptors and flat staging buffers
+        self._plans = {}
 
     def pads_d2(self, h):
         """Per-side pad amounts (top, bottom, left, right) for D2 mode:
@@ -168,256 +173,180 @@ class HaloExchanger:
         rr = hw if c < self.layout.cols - 1 else 0
         return t, b, l, rr
 
-    def exchange_padded(self, xp: torch.Tensor, h: int, off=None, nominal=None) -> None:
-        """In-place: fill xp's pad ring (width h) from neighbours.
+    def crop_d2(self, x, n):
+        """Crop n surplus pixels from each interior side (the inverse of
+        a D2 pad by n; image-boundary sides carry no surplus)."""
+        t, b, l, r = self.pads_d2(n)
+        H, W = x.shape[-2], x.shape[-1]
+        return x[:, :, t : H - b, l : W - r]
 
-        xp: (N, C, H+2h, W+2h), already zero-padded (symmetric) — or, in
-        D2 mode, padded on interior sides only, with ``off`` = (top,
-        left) pad offsets and ``nominal`` = (H, W) of the nominal
-        region. Blocks until the ring is filled (async overlap is
-        handled by HaloConv2d's interior/boundary split, not here).
+    # -- the strip plan ------------------------------------------------------
+
+    def _strips(self, H, W, h, off, grad):
+        """One _Strip per neighbour that takes part. The only place that
+        walks the neighbours.
+
+        Forward packs send_region of the padded tile and unpacks into its
+        recv_region. The transposed (``grad``) exchange runs the other
+        way: the ring band received FROM d in forward carries gradients
+        for that neighbour's interior, so recv_region is packed, and what
+        comes back belongs to the strips SENT in forward: send_region,
+        shifted by (-t0, -l0) because it is added into the UNpadded tile.
+        The receiver tags by arrival direction, so a send carries the
+        opposite of its direction of travel; gradients use tags 8..15.
         """
-        from ..utils import GLOBAL_TIMER  # noqa: F811 (cheap; cached import)
-
         hh, hw = _hpair(h)
-        if (hh == 0 and hw == 0) or not self.neigh:
-            return
+        t0, l0 = (hh, hw) if off is None else off
+        src, dst = (recv_region, send_region) if grad else (send_region, recv_region)
+        up, left, tagb = (t0, l0, 8) if grad else (0, 0, 0)
+        strips = []
+        for d, t in self.neigh:
+            if (d[0] != 0 and hh == 0) or (d[1] != 0 and hw == 0):
+                continue  # no halo along that axis
+            (ss, se), (cs, ce) = src(d, H, W, h, off)
+            (rs, re), (ks, ke) = dst(d, H, W, h, off)
+            strips.append(_Strip(
+                self.rank_of_tile(t),
+                tagb + _DIR_IDX[_opposite(d)], (ss, cs, se - ss, ce - cs),
+                tagb + _DIR_IDX[d], (rs - up, ks - left, re - rs, ke - ks),
+            ))
+        return strips
+
+    def _plan(self, xp, H, W, h, off, nominal, grad):
+        """Cached strips; for a CUDA tensor also the pack/unpack
+        descriptors and the flat staging buffers with one view per strip,
+        so a call allocates nothing."""
+        key = (tuple(xp.shape), _hpair(h), xp.dtype, xp.device, grad, off, nominal)
+        plan = self._plans.get(key)
+        if plan is None:
+            strips = self._strips(H, W, h, off, grad)
+            plan = self._plans[key] = {"strips": strips}
+            if xp.is_cuda and strips:
+                nc = xp.shape[0] * xp.shape[1]
+                for side in "sr":
+                    boxes = [s.send_box if side == "s" else s.recv_box for s in strips]
+                    sizes = [nc * b[2] * b[3] for b in boxes]
+                    flat = torch.empty(sum(sizes), device=xp.device, dtype=xp.dtype)
+                    plan[side + "desc"] = torch.tensor(boxes, dtype=torch.int64)
+                    plan[side + "buf"] = flat
+                    plan[side + "views"] = list(flat.split(sizes))
+        return plan
+
+    # -- begin / finish ------------------------------------------------------
+
+    def _begin(self, xp, h, off, nominal, grad):
+        """Pack and post one exchange; the returned finish() waits for it,
+        unpacks and returns the result: ``xp`` with its ring filled, or
+        for ``grad`` the unpadded tile with the neighbours' ring
+        gradients added."""
+        hh, hw = _hpair(h)
         if nominal is None:
             H, W = xp.shape[-2] - 2 * hh, xp.shape[-1] - 2 * hw
         else:
             H, W = nominal
+        out = xp
+        if grad:
+            t0, l0 = (hh, hw) if off is None else off
+            out = xp[:, :, t0 : t0 + H, l0 : l0 + W].clone(
+                memory_format=torch.contiguous_format
+            )
+        if (hh == 0 and hw == 0) or not self.neigh:
+            return lambda: out
         assert hh <= H and hw <= W, (
             f"halo ({hh},{hw}) exceeds local tile {H}x{W}: the spatial "
             "region extends past the resolution where tiling is valid - "
             "shrink spatial_size / use fewer tiles (the reference has the "
             "same constraint, it just corrupts silently)"
         )
+        plan = self._plan(xp, H, W, h, off, nominal, grad)
+        strips = plan["strips"]
+        if not strips:  # the neighbours lie along an axis without halo
+            return lambda: out
         if xp.is_cuda:
-            with GLOBAL_TIMER.phase("halo/exchange"):
-                return self._exchange_padded_gpu(xp, h, off, nominal)
-        sends, recvs = [], []
-        for d, t in self.neigh:
-            if (d[0] != 0 and hh == 0) or (d[1] != 0 and hw == 0):
-                continue  # no halo along that axis
-            peer = self.rank_of_tile(t)
-            (rs, re), (cs, ce) = send_region(d, H, W, h, off)
-            buf = xp[:, :, rs:re, cs:ce].contiguous()
-            # receiver tags by arrival direction = opposite of my send dir
-            sends.append((buf, peer, _DIR_IDX[_opposite(d)]))
-            (rs, re), (cs, ce) = recv_region(d, H, W, h, off)
-            rbuf = torch.empty(
-                (xp.shape[0], xp.shape[1], re - rs, ce - cs),
-                device=xp.device,
-                dtype=xp.dtype,
-            )
-            recvs.append((rbuf, peer, _DIR_IDX[d], (rs, re, cs, ce)))
+            from . import backend
+
+            ge = backend.ext()
+            ge.halo_pack(xp, plan["sbuf"], plan["sdesc"])
+            sbufs, rbufs = plan["sviews"], plan["rviews"]
+        else:
+            sbufs = [_box(xp, s.send_box).contiguous() for s in strips]
+            rbufs = [xp.new_empty(xp.shape[:2] + s.recv_box[2:]) for s in strips]
         tr = p2p.exchange(
-            [(b, p, t) for b, p, t in sends],
-            [(b, p, t) for b, p, t, _ in recvs],
+            [(b, s.peer, s.send_tag) for b, s in zip(sbufs, strips)],
+            [(b, s.peer, s.recv_tag) for b, s in zip(rbufs, strips)],
         )
-        tr.wait()
-        for rbuf, _, _, (rs, re, cs, ce) in recvs:
-            xp[:, :, rs:re, cs:ce].copy_(rbuf)
 
-    def exchange_padded_async(self, xp: torch.Tensor, h):
-        """Start the ring exchange and return a finish() callable.
+        def finish():
+            tr.wait()
+            if xp.is_cuda:
+                unpack = ge.halo_unpack_add if grad else ge.halo_unpack
+                unpack(out, plan["rbuf"], plan["rdesc"])
+            else:
+                for b, s in zip(rbufs, strips):
+                    if grad:
+                        _box(out, s.recv_box).add_(b)
+                    else:
+                        _box(out, s.recv_box).copy_(b)
+            return out
 
-        Used by the halo/compute overlap path (HaloConv2d drop mode):
+        return finish
+
+    def exchange_padded_async(self, xp: torch.Tensor, h, off=None, nominal=None):
+        """Start filling xp's pad ring (width h) from the neighbours and
+        return a finish() callable.
+
+        xp: (N, C, H+2h, W+2h), already zero-padded (symmetric) — or, in
+        D2 mode, padded on interior sides only, with ``off`` = (top,
+        left) pad offsets and ``nominal`` = (H, W) of the nominal region.
+
+        Used by the halo/compute overlap path (_overlap_halo_apply):
         pack+send/recv are issued now; finish() waits the transfer and
         unpacks the ring, AFTER the caller has queued interior compute.
         On RCCL everything is stream-ordered; the comm rides RCCL's own
         streams so the interior conv overlaps the wire time.
         """
-        hh, hw = _hpair(h)
-        if (hh == 0 and hw == 0) or not self.neigh:
-            return lambda: None
-        if xp.is_cuda:
-            from . import backend
+        return self._begin(xp, h, off, nominal, grad=False)
 
-            ge = backend.ext()
-            pl = self._plan_gpu(xp, h, grad=False)
-            ge.halo_pack(xp, pl["sbuf"], pl["sdesc"])
-            tr = p2p.exchange(
-                [(pl["sbuf"].narrow(0, o, sz), peer, tag)
-                 for peer, tag, o, sz in pl["sends"]],
-                [(pl["rbuf"].narrow(0, o, sz), peer, tag)
-                 for peer, tag, o, sz in pl["recvs"]],
-            )
+    def exchange_padded(self, xp: torch.Tensor, h, off=None, nominal=None) -> None:
+        """In-place, blocking exchange_padded_async."""
+        from ..utils import GLOBAL_TIMER  # noqa: F811 (cheap; cached import)
 
-            def finish():
-                tr.wait()
-                ge.halo_unpack(xp, pl["rbuf"], pl["rdesc"])
-
-            return finish
-        # CPU: same structure with torch packing
-        H, W = xp.shape[-2] - 2 * hh, xp.shape[-1] - 2 * hw
-        sends, recvs = [], []
-        for d, t in self.neigh:
-            if (d[0] != 0 and hh == 0) or (d[1] != 0 and hw == 0):
-                continue
-            peer = self.rank_of_tile(t)
-            (rs, re), (cs, ce) = send_region(d, H, W, h)
-            sends.append((xp[:, :, rs:re, cs:ce].contiguous(), peer,
-                          _DIR_IDX[_opposite(d)]))
-            (rs, re), (cs, ce) = recv_region(d, H, W, h)
-            rbuf = torch.empty(
-                (xp.shape[0], xp.shape[1], re - rs, ce - cs),
-                device=xp.device, dtype=xp.dtype,
-            )
-            recvs.append((rbuf, peer, _DIR_IDX[d], (rs, re, cs, ce)))
-        tr = p2p.exchange(
-            [(b, pp, t) for b, pp, t in sends],
-            [(b, pp, t) for b, pp, t, _ in recvs],
-        )
-
-        def finish():
-            tr.wait()
-            for rbuf, _, _, (rs, re, cs, ce) in recvs:
-                xp[:, :, rs:re, cs:ce].copy_(rbuf)
-
-        return finish
-
-    # -- GPU fast path: gemscore pack/unpack + flat staging buffers ---------
-
-    def _plan_gpu(self, xp, h, grad: bool, off=None, nominal=None):
-        """Cached (descs, flat buffers, per-strip views, peers/tags)."""
-        key = (tuple(xp.shape), _hpair(h), xp.dtype, grad, off, nominal)
-        cache = getattr(self, "_gpu_plans", None)
-        if cache is None:
-            cache = self._gpu_plans = {}
-        if key in cache:
-            return cache[key]
-        hh, hw = _hpair(h)
-        if nominal is None:
-            H, W = xp.shape[-2] - 2 * hh, xp.shape[-1] - 2 * hw
+        if xp.is_cuda and any(_hpair(h)) and self.neigh:
+            with GLOBAL_TIMER.phase("halo/exchange"):
+                self.exchange_padded_async(xp, h, off, nominal)()
         else:
-            H, W = nominal
-        t0, l0 = (hh, hw) if off is None else off
-        n, c = xp.shape[0], xp.shape[1]
-        tagb = 8 if grad else 0
-        out_rows, in_rows, sends, recvs = [], [], [], []
-        s_off = r_off = 0
-        for d, t in self.neigh:
-            if (d[0] != 0 and hh == 0) or (d[1] != 0 and hw == 0):
-                continue
-            peer = self.rank_of_tile(t)
-            # forward: pack send_region / unpack recv_region.
-            # grad (transposed): pack recv_region / unpack-add send_region.
-            (rs, re), (cs, ce) = (recv_region if grad else send_region)(
-                d, H, W, h, off
-            )
-            sz = n * c * (re - rs) * (ce - cs)
-            out_rows.append([rs, cs, re - rs, ce - cs])
-            sends.append((peer, tagb + _DIR_IDX[_opposite(d)], s_off, sz))
-            s_off += sz
-            (rs, re), (cs, ce) = (send_region if grad else recv_region)(
-                d, H, W, h, off
-            )
-            sz = n * c * (re - rs) * (ce - cs)
-            if grad:
-                # unpack-add targets the UNpadded grad tile
-                in_rows.append([rs - t0, cs - l0, re - rs, ce - cs])
-            else:
-                in_rows.append([rs, cs, re - rs, ce - cs])
-            recvs.append((peer, tagb + _DIR_IDX[d], r_off, sz))
-            r_off += sz
-        plan = {
-            "sdesc": torch.tensor(out_rows, dtype=torch.int64),
-            "rdesc": torch.tensor(in_rows, dtype=torch.int64),
-            "sbuf": torch.empty(s_off, device=xp.device, dtype=xp.dtype),
-            "rbuf": torch.empty(r_off, device=xp.device, dtype=xp.dtype),
-            "sends": sends,
-            "recvs": recvs,
-        }
-        cache[key] = plan
-        return plan
+            self.exchange_padded_async(xp, h, off, nominal)()
 
-    def _exchange_padded_gpu(self, xp, h, off=None, nominal=None):
-        from . import backend
-
-        ge = backend.ext()
-        pl = self._plan_gpu(xp, h, grad=False, off=off, nominal=nominal)
-        ge.halo_pack(xp, pl["sbuf"], pl["sdesc"])
-        tr = p2p.exchange(
-            [(pl["sbuf"].narrow(0, o, s), peer, tag) for peer, tag, o, s in pl["sends"]],
-            [(pl["rbuf"].narrow(0, o, s), peer, tag) for peer, tag, o, s in pl["recvs"]],
-        )
-        tr.wait()
-        ge.halo_unpack(xp, pl["rbuf"], pl["rdesc"])
-
-    def _exchange_grad_padded_gpu(self, gp, h, off=None, nominal=None):
-        from . import backend
-
-        ge = backend.ext()
-        hh, hw = _hpair(h)
-        if nominal is None:
-            H, W = gp.shape[-2] - 2 * hh, gp.shape[-1] - 2 * hw
-            t0, l0 = hh, hw
-        else:
-            H, W = nominal
-            t0, l0 = off
-        g = gp[:, :, t0 : t0 + H, l0 : l0 + W].clone().contiguous()
-        pl = self._plan_gpu(gp, h, grad=True, off=off, nominal=nominal)
-        ge.halo_pack(gp, pl["sbuf"], pl["sdesc"])
-        tr = p2p.exchange(
-            [(pl["sbuf"].narrow(0, o, s), peer, tag) for peer, tag, o, s in pl["sends"]],
-            [(pl["rbuf"].narrow(0, o, s), peer, tag) for peer, tag, o, s in pl["recvs"]],
-        )
-        tr.wait()
-        ge.halo_unpack_add(g, pl["rbuf"], pl["rdesc"])
-        return g
-
-    # -- backward (transposed) ------------------------------------------------
-
-    def exchange_grad_padded(
-        self, gp: torch.Tensor, h: int, off=None, nominal=None
-    ) -> torch.Tensor:
-        """Transposed halo exchange: return grad wrt the UNpadded tile.
+    def exchange_grad_padded_async(self, gp: torch.Tensor, h, off=None, nominal=None):
+        """Start the transposed halo exchange; finish() returns the grad
+        wrt the UNpadded tile.
 
         gp: gradient wrt the padded tile (N, C, H+2h, W+2h). The pad-ring
         bands belong to neighbours' interior pixels: send each band to its
         owner; add received bands into my interior edge regions.
         """
-        hh, hw = _hpair(h)
-        if nominal is None:
-            H, W = gp.shape[-2] - 2 * hh, gp.shape[-1] - 2 * hw
-            t0, l0 = hh, hw
-        else:
-            H, W = nominal
-            t0, l0 = off
-        if ((hh or hw) and self.neigh) and gp.is_cuda:
-            return self._exchange_grad_padded_gpu(gp, h, off, nominal)
-        g = gp[:, :, t0 : t0 + H, l0 : l0 + W].clone()
-        if (hh == 0 and hw == 0) or not self.neigh:
-            return g
-        sends, recvs = [], []
-        for d, t in self.neigh:
-            if (d[0] != 0 and hh == 0) or (d[1] != 0 and hw == 0):
-                continue
-            peer = self.rank_of_tile(t)
-            # the band I received FROM d in forward carries grads for the
-            # neighbour's interior: send it back tagged with my direction
-            # as seen by the receiver (= opposite(d)).
-            (rs, re), (cs, ce) = recv_region(d, H, W, h, off)
-            buf = gp[:, :, rs:re, cs:ce].contiguous()
-            sends.append((buf, peer, 8 + _DIR_IDX[_opposite(d)]))
-            # I get back grads for the strips I SENT in forward
-            (rs, re), (cs, ce) = send_region(d, H, W, h, off)
-            rbuf = torch.empty(
-                (gp.shape[0], gp.shape[1], re - rs, ce - cs),
-                device=gp.device,
-                dtype=gp.dtype,
-            )
-            recvs.append((rbuf, peer, 8 + _DIR_IDX[d], (rs, re, cs, ce)))
-        tr = p2p.exchange(
-            [(b, p, t) for b, p, t in sends],
-            [(b, p, t) for b, p, t, _ in recvs],
-        )
-        tr.wait()
-        for rbuf, _, _, (rs, re, cs, ce) in recvs:
-            # send_region coords are in padded space; shift to unpadded
-            g[:, :, rs - t0 : re - t0, cs - l0 : ce - l0].add_(rbuf)
-        return g
+        return self._begin(gp, h, off, nominal, grad=True)
+
+    def exchange_grad_padded(
+        self, gp: torch.Tensor, h, off=None, nominal=None
+    ) -> torch.Tensor:
+        """Blocking exchange_grad_padded_async."""
+        return self.exchange_grad_padded_async(gp, h, off, nominal)()
+
+
+def exchanger_for(
+    num_spatial_parts, slice_method, spatial_local_rank, rank_of_tile=None, **_
+):
+    """The HaloExchanger of one tile, from the keys of a plan ctx
+    (``exchanger_for(**ctx)``); None where there is a single tile.
+    ``rank_of_tile=None``: tile index == global rank (tests)."""
+    if num_spatial_parts <= 1:
+        return None
+    if rank_of_tile is None:
+        rank_of_tile = lambda t: t  # noqa: E731
+    return HaloExchanger(
+        TileLayout(num_spatial_parts, slice_method), spatial_local_rank, rank_of_tile
+    )
 
 
 class _HaloPadFn(torch.autograd.Function):

@@ -31,7 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .conv_native import NativeConv2d
-from .halo import HaloExchanger, TileLayout, halo_pad
+from .halo import TileLayout, _hpair, exchanger_for, halo_pad
 
 
 def outer_pad_only(x: torch.Tensor, layout: TileLayout, tile: int, pad, fill: float = 0.0):
@@ -100,12 +100,8 @@ class _SpatialBase(nn.Module):
         self.layout = TileLayout(num_spatial_parts, slice_method)
         self.tile = spatial_local_rank
         self.grad_mode = grad_mode
-        if rank_of_tile is None:
-            rank_of_tile = lambda t: t  # tile index == global rank (tests)
-        self.exchanger = (
-            HaloExchanger(self.layout, self.tile, rank_of_tile)
-            if num_spatial_parts > 1
-            else None
+        self.exchanger = exchanger_for(
+            num_spatial_parts, slice_method, spatial_local_rank, rank_of_tile
         )
 
 
@@ -141,14 +137,13 @@ class HaloConv2d(_SpatialBase):
         super().__init__(
             num_spatial_parts, slice_method, spatial_local_rank, rank_of_tile, grad_mode
         )
-        kh, kw = (kernel_size, kernel_size) if isinstance(kernel_size, int) else kernel_size
-        if padding is None:
-            padding = ((kh - 1) // 2, (kw - 1) // 2)
-        elif isinstance(padding, int):
-            padding = (padding, padding)
-        self.halo_len = tuple(padding) if halo_len is None else halo_len
+        # int-or-pair arguments are expanded here, once: _kernel, _halo
+        self._kernel = kh, kw = _hpair(kernel_size)
+        padding = ((kh - 1) // 2, (kw - 1) // 2) if padding is None else _hpair(padding)
+        self.halo_len = padding if halo_len is None else halo_len
+        self._halo = _hpair(self.halo_len)
         self.d2 = d2
-        self.outer_pad = tuple(padding) if d2 else (0, 0)
+        self.outer_pad = padding if d2 else (0, 0)
         self.conv = NativeConv2d(
             in_channels, out_channels, kernel_size, stride=stride, padding=0, bias=bias
         )
@@ -156,23 +151,14 @@ class HaloConv2d(_SpatialBase):
         self.kernel_size = kernel_size
 
     def forward(self, x):
-        if self.d2 and self.halo_len in (0, (0, 0)):
+        if self.d2 and self._halo == (0, 0):
             if self.exchanger is not None:
                 xp = outer_pad_only(x, self.layout, self.tile, self.outer_pad)
             else:
                 ph, pw = self.outer_pad
                 xp = F.pad(x, (pw, pw, ph, ph))
         else:
-            hh, hw = (
-                self.halo_len
-                if isinstance(self.halo_len, tuple)
-                else (self.halo_len, self.halo_len)
-            )
-            kh, kw = (
-                (self.kernel_size, self.kernel_size)
-                if isinstance(self.kernel_size, int)
-                else self.kernel_size
-            )
+            (hh, hw), (kh, kw) = self._halo, self._kernel
             if (
                 self.exchanger is not None
                 and not x.is_meta
@@ -207,13 +193,8 @@ class HaloConv2d(_SpatialBase):
         transposed halo-gradient exchange — same trajectory as the
         blocking exact path, with the forward ring overlapped.
         """
-        hh, hw = (
-            self.halo_len
-            if isinstance(self.halo_len, tuple)
-            else (self.halo_len, self.halo_len)
-        )
         return _overlap_halo_apply(
-            self.conv, x, hh, hw, self.exchanger, self.grad_mode
+            self.conv, x, *self._halo, self.exchanger, self.grad_mode
         )
 
 
