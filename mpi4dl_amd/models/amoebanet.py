@@ -22,6 +22,12 @@ amoebanet.py:318-336); everything else here is our own implementation:
 
 Cells pass ``(x, skip)`` tuples between stages — the pipeline and every
 spatial seam handle multi-tensor activations.
+
+The fused-halo variant (models/amoebanet_d2.py, "D2") has no cell, op
+body or builder of its own: ``Cell`` has two override points (op
+construction, and a step on an op's input), ``make_op`` takes what a D2
+conv op changes as arguments, and ``build_amoebanetd`` takes the cell
+class.
 """
 
 from __future__ import annotations
@@ -31,7 +37,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from ..ops.plan import SpatialPlan
+from ..ops.plan import SpatialPlan, plan_hooks
 from ..ops.spatial_conv import HaloConv2d, HaloPool2d
 
 Tensor = torch.Tensor
@@ -129,8 +135,34 @@ def _bn_relu(mknorm, ch):
     return nn.Sequential(bn, nn.ReLU(inplace=False))
 
 
+def _bn_margin(bn, margin):
+    """BN (possibly wrapped by _bn_relu) whose batch statistics skip the
+    surplus ``margin`` of its input."""
+    if any(margin):
+        target = bn[0] if isinstance(bn, nn.Sequential) else bn
+        if not hasattr(target, "stat_margin"):
+            raise TypeError(
+                f"{type(target).__name__} cannot exclude a surplus margin "
+                "from its statistics; D2 spatial cells need TileBatchNorm2d"
+            )
+        target.stat_margin = tuple(margin)
+    return bn
+
+
+_NO_MARGIN = (0, 0, 0, 0)
+
+
 def make_op(name: str, c: int, stride: int, ctx, mknorm,
-            ref_quirks: bool = False) -> nn.Module:
+            ref_quirks: bool = False, *, pw=None, conv=_conv,
+            margins=(_NO_MARGIN, _NO_MARGIN)) -> nn.Module:
+    """One genotype op. The keyword arguments are what a fused-halo (D2)
+    conv op changes (models/amoebanet_d2.py): ``pw`` is the class of the
+    1x1 convs of the conv_3x3 / conv_1x7_7x1 bodies (None: NativeConv2d),
+    ``conv`` the factory of their k x k convs, ``margins`` the surplus
+    (top, bottom, left, right) that the input of their first and second
+    BN still carries and that its statistics leave out."""
+    if pw is None:
+        from ..ops.conv_native import NativeConv2d as pw
     if name == "none":
         return (
             nn.Identity() if stride == 1 else FactorizedReduce(c, c, mknorm)
@@ -168,32 +200,29 @@ def make_op(name: str, c: int, stride: int, ctx, mknorm,
             mknorm(c),
         )
     if name == "conv_3x3":
-        from ..ops.conv_native import NativeConv2d
-
         return nn.Sequential(
-            NativeConv2d(c, c // 4, 1, bias=False),
+            pw(c, c // 4, 1, bias=False),
+            _bn_margin(_bn_relu(mknorm, c // 4), margins[0]),
+            nn.Identity(),
+            conv(c // 4, c // 4, (3, 3), stride=stride, padding=(1, 1), ctx=ctx),
             _bn_relu(mknorm, c // 4),
             nn.Identity(),
-            _conv(c // 4, c // 4, 3, stride=stride, ctx=ctx),
-            _bn_relu(mknorm, c // 4),
-            nn.Identity(),
-            NativeConv2d(c // 4, c, 1, bias=False),
+            pw(c // 4, c, 1, bias=False),
             mknorm(c),
         )
     if name == "conv_1x7_7x1":
-        from ..ops.conv_native import NativeConv2d
-
+        # the 1x7 consumes the column surplus, the 7x1 the row surplus
         return nn.Sequential(
-            NativeConv2d(c, c // 4, 1, stride=1, bias=False),
+            pw(c, c // 4, 1, stride=1, bias=False),
+            _bn_margin(_bn_relu(mknorm, c // 4), margins[0]),
+            nn.Identity(),
+            conv(c // 4, c // 4, (1, 7), stride=(1, stride), padding=(0, 3), ctx=ctx),
+            _bn_margin(_bn_relu(mknorm, c // 4), margins[1]),
+            nn.Identity(),
+            conv(c // 4, c // 4, (7, 1), stride=(stride, 1), padding=(3, 0), ctx=ctx),
             _bn_relu(mknorm, c // 4),
             nn.Identity(),
-            _conv(c // 4, c // 4, (1, 7), stride=(1, stride), padding=(0, 3), ctx=ctx),
-            _bn_relu(mknorm, c // 4),
-            nn.Identity(),
-            _conv(c // 4, c // 4, (7, 1), stride=(stride, 1), padding=(3, 0), ctx=ctx),
-            _bn_relu(mknorm, c // 4),
-            nn.Identity(),
-            NativeConv2d(c // 4, c, 1, stride=1, bias=False),
+            pw(c // 4, c, 1, stride=1, bias=False),
             mknorm(c),
         )
     raise ValueError(f"unknown op {name}")
@@ -240,7 +269,21 @@ class Cell(nn.Module):
     """One AmoebaNet cell (reference Cell :449-533): takes (s1, s2) — or a
     single tensor used for both — reduces them to ``channels``, applies the
     5 genotype pairs, concats the selected states; returns (out, skip=s1_in).
+
+    A variant (amoebanet_d2.CellD2) overrides how an op is built and what
+    is done to an op's input; the constructor body and the forward loop
+    exist here only.
     """
+
+    # and-ed with ops/fuse.glue_enabled(): state_fan / shared_relu hand
+    # out plain aliases of a state, which is all this cell's ops read
+    uses_glue = True
+    _make_op = staticmethod(make_op)
+
+    def _op_input(self, pos: int, t: Tensor, cache: dict) -> Tensor:
+        """What op ``pos`` reads, given its input state ``t`` (after the
+        ReLU where the op wants one). ``cache`` lives for one forward."""
+        return t
 
     def __init__(
         self,
@@ -270,12 +313,12 @@ class Cell(nn.Module):
         self._cat_only = frozenset(
             i for i in self.concat if i >= 2 and i not in set(self.indices)
         )
+        self.op_strides = [2 if (reduction and i < 2) else 1 for i, _ in ops]
         self.operations = nn.ModuleList()
-        for i, name in ops:
-            stride = 2 if (reduction and i < 2) else 1
+        for (_, name), stride in zip(ops, self.op_strides):
             self.operations.append(
-                make_op(name, channels, stride, ctx, mknorm,
-                        ref_quirks=ref_quirks)
+                self._make_op(name, channels, stride, ctx, mknorm,
+                              ref_quirks=ref_quirks)
             )
         self._fans = self._fan_plan()
 
@@ -321,12 +364,13 @@ class Cell(nn.Module):
         else:
             s1 = s2 = input_or_states
         skip = s1
-        glue = glue_enabled()
+        glue = self.uses_glue and glue_enabled()
         states = [
             _reduce(self.reduce1, s1, glue), _reduce(self.reduce2, s2, glue)
         ]
         relu_cache = {}
         fans = {}
+        cache = {}
 
         def get(idx, key, want_relu):
             if glue and idx in self._fans:
@@ -340,12 +384,14 @@ class Cell(nn.Module):
                 relu_cache[idx] = torch.relu(states[idx])
             return relu_cache[idx]
 
+        def run(pos):
+            t = get(self.indices[pos], pos, self.wants_relu[pos])
+            return self.operations[pos](self._op_input(pos, t, cache))
+
         pending = {}
         for i in range(0, len(self.operations), 2):
-            h1 = self.operations[i](get(self.indices[i], i, self.wants_relu[i]))
-            h2 = self.operations[i + 1](
-                get(self.indices[i + 1], i + 1, self.wants_relu[i + 1])
-            )
+            h1 = run(i)
+            h2 = run(i + 1)
             sidx = 2 + i // 2
             if sidx in self._cat_only:
                 pending[sidx] = (h1, h2)
@@ -376,17 +422,11 @@ class Classify(nn.Module):
 # ---------------------------------------------------------------------------
 
 
-def amoebanetd(
-    num_classes: int = 10,
-    num_layers: int = 6,
-    num_filters: int = 64,
-    plan: Optional[SpatialPlan] = None,
-    ref_quirks: bool = False,
-) -> nn.Sequential:
-    """AmoebaNet-D as a flat Sequential of cells (reference :535-616).
-    ``plan`` != None builds the spatial variant (reference
-    amoebanetd_spatial :618-737) — halo ops + tile-synced BN on the
-    cells assigned to spatial partitions."""
+def build_amoebanetd(cell_cls, num_classes, num_layers, num_filters, plan,
+                     ref_quirks) -> nn.Sequential:
+    """The one builder body: stem, cells of ``cell_cls``, classifier."""
+    from ..ops.norm import TileBatchNorm2d
+
     assert num_layers % 3 == 0, "num_layers must be divisible by 3"
     repeat = num_layers // 3
 
@@ -398,23 +438,13 @@ def amoebanetd(
         "red_prev": False,
     }
     cells: List[nn.Module] = []
-
-    def ctx():
-        return plan.ctx(len(cells)) if plan is not None else None
-
-    def mknorm():
-        if plan is None:
-            # TileBatchNorm2d(group=None) == BatchNorm2d numerically but
-            # takes the gemscore fused path on GPU
-            from ..ops.norm import TileBatchNorm2d
-
-            return TileBatchNorm2d
-        i = len(cells)
-        return lambda ch: plan.norm(ch, i)
+    # TileBatchNorm2d(group=None) == BatchNorm2d numerically but takes the
+    # gemscore fused path on GPU
+    ctx, mknorm = plan_hooks(plan, cells, TileBatchNorm2d)
 
     def add_cell(reduction: bool, scale: int):
         state["c"] *= scale
-        cell = Cell(
+        cell = cell_cls(
             state["c_pp"],
             state["c_p"],
             state["c"],
@@ -442,6 +472,21 @@ def amoebanetd(
         add_cell(False, 1)
     cells.append(Classify(state["c_p"], num_classes))
     return nn.Sequential(*cells)
+
+
+def amoebanetd(
+    num_classes: int = 10,
+    num_layers: int = 6,
+    num_filters: int = 64,
+    plan: Optional[SpatialPlan] = None,
+    ref_quirks: bool = False,
+) -> nn.Sequential:
+    """AmoebaNet-D as a flat Sequential of cells (reference :535-616).
+    ``plan`` != None builds the spatial variant (reference
+    amoebanetd_spatial :618-737) — halo ops + tile-synced BN on the
+    cells assigned to spatial partitions."""
+    return build_amoebanetd(Cell, num_classes, num_layers, num_filters, plan,
+                            ref_quirks)
 
 
 def amoebanetd_spatial(

@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch.nn as nn
 
-from ..ops.plan import SpatialPlan
+from ..ops.plan import SpatialPlan, plan_hooks
 from ..ops.conv_native import NativeConv2d
 from ..ops.spatial_conv import HaloConv2d, HaloPool2d
 from .resnet import Head  # noqa: F401
@@ -115,19 +115,17 @@ class StemS(nn.Module):
         return self.ops(x)
 
 
+def _v2_block(group, block, ch, mid, out, stride, ctx, mknorm, preact):
+    return BottleneckV2S(ch, mid, out, stride, ctx, mknorm, preact=preact)
+
+
 def _build(input_shape, num_classes, n, num_filters, plan, version,
-           ref_stem=False):
+           ref_stem=False, v2_block=_v2_block):
+    """``v2_block``: the factory of one version-2 block, called with what
+    the schedule loop knows (resnet_spatial_d2 supplies its own)."""
     _, in_ch, H, W = input_shape
     cells = []
-
-    def ctx():
-        return plan.ctx(len(cells)) if plan is not None else None
-
-    def mknorm():
-        if plan is None:
-            return nn.BatchNorm2d
-        i = len(cells)
-        return lambda ch: plan.norm(ch, i)
+    ctx, mknorm = plan_hooks(plan, cells, nn.BatchNorm2d)
 
     cells.append(StemS(in_ch, num_filters, min(H, W), ctx(), mknorm(),
                        ref_stem=ref_stem))
@@ -145,9 +143,9 @@ def _build(input_shape, num_classes, n, num_filters, plan, version,
             out = mid * (4 if group == 0 else 2)
             for block in range(n):
                 stride = 2 if (group > 0 and block == 0) else 1
-                cells.append(BottleneckV2S(
-                    ch, mid, out, stride, ctx(), mknorm(),
-                    preact=not (group == 0 and block == 0),
+                cells.append(v2_block(
+                    group, block, ch, mid, out, stride, ctx(), mknorm(),
+                    not (group == 0 and block == 0),
                 ))
                 ch = out
     cells.append(Head(ch, num_classes, final_bn=(version == 2), mknorm=mknorm()))
@@ -177,15 +175,7 @@ def get_resnet101_cells(
     models/resnet.py:get_resnet101_cells."""
     _, in_ch, H, W = input_shape
     cells = []
-
-    def ctx():
-        return plan.ctx(len(cells)) if plan is not None else None
-
-    def mknorm():
-        if plan is None:
-            return nn.BatchNorm2d
-        i = len(cells)
-        return lambda ch: plan.norm(ch, i)
+    ctx, mknorm = plan_hooks(plan, cells, nn.BatchNorm2d)
 
     cells.append(StemS(in_ch, width, min(H, W), ctx(), mknorm()))
     ch = width

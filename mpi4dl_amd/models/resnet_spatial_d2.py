@@ -32,8 +32,7 @@ import torch.nn as nn
 from ..ops.halo import TileLayout, exchanger_for, halo_pad_d2
 from ..ops.plan import SpatialPlan
 from ..ops.spatial_conv import outer_pad_only
-from .resnet import Head
-from .resnet_spatial import BottleneckV2S, StemS
+from .resnet_spatial import BottleneckV2S, _build
 
 
 class CropInterior(nn.Module):
@@ -105,53 +104,27 @@ def get_resnet_v2(
     """D2 ResNet v2: cell layout identical to resnet/resnet_spatial v2
     builders (stem + 3n bottlenecks + head); spatial cells inside
     stride-1 runs use the fused-halo design."""
-    _, in_ch, H, W = input_shape
-    cells = []
+    surplus_left = 0  # blocks the last fused exchange still feeds
 
-    def ctx():
-        return plan.ctx(len(cells)) if plan is not None else None
+    def block_d2(group, block, ch, mid, out, stride, ctx, mknorm, preact):
+        nonlocal surplus_left
+        d1_style = (
+            ctx is None
+            or stride != 1
+            or block == 0  # channel-change block: keep D1 (has proj)
+        )
+        if d1_style:
+            surplus_left = 0
+            return BottleneckV2S(ch, mid, out, stride, ctx, mknorm,
+                                 preact=preact)
+        pre_h = 0
+        if surplus_left == 0:
+            # 2 surplus pixels per fused block (two 3x3 convs)
+            nblk = min(fused_layers, n - block)
+            pre_h = 2 * nblk
+            surplus_left = nblk
+        surplus_left -= 1
+        return BottleneckV2D2(ch, mid, out, ctx, mknorm, pre_h=pre_h)
 
-    def mknorm():
-        if plan is None:
-            return nn.BatchNorm2d
-        i = len(cells)
-        return lambda ch: plan.norm(ch, i)
-
-    cells.append(StemS(in_ch, num_filters, min(H, W), ctx(), mknorm(),
-                       ref_stem=ref_stem))
-    ch = num_filters
-    mid = num_filters
-    for group in range(3):
-        # reference width schedule: stage 0 expands 4x (stride 1), later
-        # stages 2x with stride 2 at block 0 (resnet.py:288-300)
-        out_ch = mid * (4 if group == 0 else 2)
-        surplus_left = 0
-        for block in range(n):
-            stride = 2 if (group > 0 and block == 0) else 1
-            c = ctx()
-            d1_style = (
-                c is None
-                or stride != 1
-                or block == 0  # channel-change block: keep D1 (has proj)
-            )
-            if d1_style:
-                cells.append(BottleneckV2S(
-                    ch, mid, out_ch, stride, c, mknorm(),
-                    preact=not (group == 0 and block == 0),
-                ))
-                surplus_left = 0
-            else:
-                pre_h = 0
-                if surplus_left == 0:
-                    # 2 surplus pixels per fused block (two 3x3 convs)
-                    nblk = min(fused_layers, n - block)
-                    pre_h = 2 * nblk
-                    surplus_left = nblk
-                cells.append(
-                    BottleneckV2D2(ch, mid, out_ch, c, mknorm(), pre_h=pre_h)
-                )
-                surplus_left -= 1
-            ch = out_ch
-        mid = out_ch
-    cells.append(Head(ch, num_classes, final_bn=True, mknorm=mknorm()))
-    return nn.Sequential(*cells)
+    return _build(input_shape, num_classes, n, num_filters, plan, version=2,
+                  ref_stem=ref_stem, v2_block=block_d2)

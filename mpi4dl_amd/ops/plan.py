@@ -11,7 +11,9 @@ resnet_spatial.py:272-297). Here one object owns the mapping:
   (spatial.py:913-918).
 
 Model builders call ``plan.ctx(cell_idx)`` and get either None (build a
-plain op) or kwargs for HaloConv2d / HaloPool2d / HaloExchangeLayer.
+plain op) or kwargs for HaloConv2d / HaloPool2d / HaloExchangeLayer;
+``plan_hooks`` wraps that and ``plan.norm`` for a builder's growing list
+of cells, with or without a plan.
 """
 
 from __future__ import annotations
@@ -102,3 +104,21 @@ class SpatialPlan:
         if g is None and self.partition_of_cell(cell_idx) >= self.comm.spatial_size:
             return nn.BatchNorm2d(num_features)
         return TileBatchNorm2d(num_features, group=g)
+
+
+def plan_hooks(plan: Optional[SpatialPlan], cells: list, default_norm):
+    """The two questions a model builder asks while it appends to
+    ``cells``, about the cell it is about to append: ``ctx()`` gives the
+    halo-op kwargs (None = plain ops), ``mknorm()`` the norm factory
+    (``default_norm`` without a plan)."""
+
+    def ctx():
+        return plan.ctx(len(cells)) if plan is not None else None
+
+    def mknorm():
+        if plan is None:
+            return default_norm
+        i = len(cells)
+        return lambda ch: plan.norm(ch, i)
+
+    return ctx, mknorm
