@@ -393,9 +393,15 @@ def sync_comms_for_master(comm1: Communicator, comm2: Communicator):
 class FlatGrads:
     """Make every parameter's .grad a view into ONE flat buffer.
 
-    Autograd then accumulates straight into the buffer: reduction is a
+    Gradients then accumulate straight into the buffer: reduction is a
     single all_reduce with zero pack/unpack work per step (the reference
     re-concatenates all grads every step — comm.py:414-438).
+
+    Who adds into a view: the hand-written weight-gradient kernels
+    themselves (conv pw_bwdw / conv_bwd_weight, BatchNorm backward) for
+    the parameters opted in here, as long as ``ops.grad_sink.grad_sink``
+    allows it (no hooks on the parameter, plain backward); autograd's
+    AccumulateGrad for every other gradient.
     """
 
     def __init__(
@@ -404,6 +410,8 @@ class FlatGrads:
         dtype: Optional[torch.dtype] = None,
         pad_to: int = 0,
     ):
+        from .ops.grad_sink import opt_in
+
         self.params = [p for p in module.parameters() if p.requires_grad]
         if not self.params:
             self.buffer = torch.zeros(0)
@@ -420,6 +428,7 @@ class FlatGrads:
             if p.grad is not None:
                 view.copy_(p.grad)  # keep grads accumulated before attach
             p.grad = view
+            opt_in(p)  # backward kernels may add into the view in place
             offset += n
 
     def zero_(self):

@@ -748,9 +748,12 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor w,
   return out;
 }
 
+// With `out` (fp32, contiguous, K*C*R*S elements, go's device) the kernel's
+// atomicAdd accumulates into it; without, into a fresh zeroed tensor.
 torch::Tensor conv_bwd_weight(torch::Tensor go, torch::Tensor x,
                               int64_t R, int64_t S, int64_t sh, int64_t sw,
-                              int64_t ph, int64_t pw) {
+                              int64_t ph, int64_t pw,
+                              c10::optional<torch::Tensor> out) {
   TORCH_CHECK(go.is_cuda() && go.is_contiguous() && x.is_contiguous());
   TORCH_CHECK(go.scalar_type() == torch::kBFloat16 &&
               x.scalar_type() == torch::kBFloat16);
@@ -758,8 +761,18 @@ torch::Tensor conv_bwd_weight(torch::Tensor go, torch::Tensor x,
                                go.size(1), R, S, sh, sw, ph, pw);
   TORCH_CHECK(go.size(0) == g.N && go.size(2) == g.OH && go.size(3) == g.OW,
               "conv_bwd_weight: go is not the gradient of this convolution");
-  auto gw = torch::zeros({(int64_t)g.K, (int64_t)g.CRS},
-                         x.options().dtype(torch::kFloat));
+  torch::Tensor gw;
+  if (out.has_value()) {
+    gw = *out;
+    TORCH_CHECK(gw.is_cuda() && gw.get_device() == go.get_device() &&
+                    gw.scalar_type() == torch::kFloat && gw.is_contiguous() &&
+                    gw.numel() == (int64_t)g.K * g.CRS,
+                "conv_bwd_weight: out must be a contiguous fp32 tensor of "
+                "K*C*R*S elements on go's device");
+  } else {
+    gw = torch::zeros({(int64_t)g.K, (int64_t)g.CRS},
+                      x.options().dtype(torch::kFloat));
+  }
   const int m_tiles = (g.K + WBM - 1) / WBM;
   const int n_tiles = (g.CRS + WBN - 1) / WBN;
   const int64_t blocks = (int64_t)m_tiles * n_tiles * g.N * g.OH;
@@ -776,8 +789,12 @@ torch::Tensor conv_bwd_weight(torch::Tensor go, torch::Tensor x,
 void register_conv_mfma(pybind11::module_& m) {
   m.def("conv_fwd", &conv_mfma::conv_fwd,
         "implicit-GEMM MFMA conv forward (bf16 NCHW)");
-  m.def("conv_bwd_weight", &conv_mfma::conv_bwd_weight,
-        "implicit-GEMM MFMA conv weight gradient (fp32 out)");
+  m.def("conv_bwd_weight", &conv_mfma::conv_bwd_weight, pybind11::arg("go"),
+        pybind11::arg("x"), pybind11::arg("R"), pybind11::arg("S"),
+        pybind11::arg("sh"), pybind11::arg("sw"), pybind11::arg("ph"),
+        pybind11::arg("pw"), pybind11::arg("out") = pybind11::none(),
+        "implicit-GEMM MFMA conv weight gradient (fp32 out); adds into `out` "
+        "when given");
   m.def("conv_fwd_kernel_name", &conv_mfma::conv_fwd_kernel_name,
         "label of the kernel conv_fwd launches for (C, K, H, W, R, S, sh, "
         "sw, ph, pw); no tensor, no HIP call");

@@ -660,7 +660,11 @@ std::string pw_bwdw_kernel_name(int64_t N, int64_t K, int64_t C,
   return choose_bwdw(N, (int)K, (int)C, (int)OHW).label;
 }
 
-torch::Tensor pw_bwdw(torch::Tensor go, torch::Tensor x) {
+// With `out` (fp32, contiguous, K*C elements, go's device) the kernel's
+// atomicAdd accumulates into it and it is returned; without, into a fresh
+// zeroed [K, C] tensor.
+torch::Tensor pw_bwdw(torch::Tensor go, torch::Tensor x,
+                      c10::optional<torch::Tensor> out) {
   TORCH_CHECK(go.is_cuda() && go.is_contiguous() && x.is_contiguous());
   TORCH_CHECK(go.scalar_type() == torch::kBFloat16 &&
               x.scalar_type() == torch::kBFloat16);
@@ -674,8 +678,18 @@ torch::Tensor pw_bwdw(torch::Tensor go, torch::Tensor x) {
   TORCH_CHECK(g.OHW % 64 == 0, "pw_bwdw: OHW % 64");
   const BwdwChoice ch = choose_bwdw(g.Nimg, g.K, g.C, g.OHW);
   g.slab = ch.slab;
-  auto gw = torch::zeros({(int64_t)g.K, (int64_t)g.C},
-                         x.options().dtype(torch::kFloat));
+  torch::Tensor gw;
+  if (out.has_value()) {
+    gw = *out;
+    TORCH_CHECK(gw.is_cuda() && gw.get_device() == go.get_device() &&
+                    gw.scalar_type() == torch::kFloat && gw.is_contiguous() &&
+                    gw.numel() == (int64_t)g.K * g.C,
+                "pw_bwdw: out must be a contiguous fp32 tensor of K*C "
+                "elements on go's device");
+  } else {
+    gw = torch::zeros({(int64_t)g.K, (int64_t)g.C},
+                      x.options().dtype(torch::kFloat));
+  }
   launch(ch.kern, ch.blocks, 2 * ch.tile, (const bf16*)go.data_ptr(),
          (const bf16*)x.data_ptr(), gw.data_ptr<float>(), g);
   return gw;
@@ -803,8 +817,10 @@ void register_conv_pw(pybind11::module_& m) {
         "1x1 conv forward (streaming MFMA GEMM, bf16 NCHW)");
   m.def("pw_bwd_data_strided", &conv_pw::pw_bwd_data_strided,
         "1x1 strided conv backward-data (scatter epilogue)");
-  m.def("pw_bwdw", &conv_pw::pw_bwdw,
-        "1x1 stride-1 conv backward-weight (NT MFMA GEMM, fp32 out)");
+  m.def("pw_bwdw", &conv_pw::pw_bwdw, pybind11::arg("go"), pybind11::arg("x"),
+        pybind11::arg("out") = pybind11::none(),
+        "1x1 stride-1 conv backward-weight (NT MFMA GEMM, fp32 out); adds "
+        "into `out` when given");
   // what the launchers above pick, from plain integers: no tensor, no
   // HIP call
   m.def("pw_kernel_name", &conv_pw::pw_kernel_name,

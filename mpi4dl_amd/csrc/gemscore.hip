@@ -1369,7 +1369,18 @@ __device__ __forceinline__ float bn_bwd_elem(float g, float xh, float gsn,
   return (reduced ? g - gsn - xh * gxn : g) * w * inv;
 }
 
-// gi = w*inv*(g - gsum/n - xhat*gxsum/n). REGION: mean/var came from the
+// a reduction term sum/n from the fp64 statistic: the statistic is rounded
+// to fp32 first, which is what the fp32 cast of the statistics followed by
+// (float)(sum * inv_n) gave
+__device__ __forceinline__ float bn_bwd_term(double st, double inv_n) {
+  return (float)((double)(float)st * inv_n);
+}
+
+// gi = w*inv*(g - gsum/n - xhat*gxsum/n). gsum/gxsum are the (group-wide)
+// fp64 statistics. With `local` (the tile's own fp64 [gsum, gxsum]) block 0
+// also produces the parameter gradients gb = (float)local[:C], gw =
+// (float)local[C:]: added in place into gb_acc / gw_acc where given, else
+// written to pgrad[2C]. REGION: mean/var came from the
 // region pixels only while every pixel was normalised, so the two
 // reduction terms reach region pixels only:
 //   gi_p = w*inv*[g_p - 1{p in region}*(gsum/n + xhat_p*gxsum/n)]
@@ -1378,10 +1389,21 @@ __global__ void bn_bwd_apply_kernel(
     const T* __restrict__ go, const T* __restrict__ x, const T* __restrict__ y,
     T* __restrict__ gi, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ wgt,
-    const float* __restrict__ gsum, const float* __restrict__ gxsum,
-    double inv_n, int64_t total, int64_t C, int64_t HW, int W, int row_lo,
-    int row_hi, int col_lo, int col_hi) {
+    const double* __restrict__ gsum, const double* __restrict__ gxsum,
+    const double* __restrict__ local, float* __restrict__ gw_acc,
+    float* __restrict__ gb_acc, float* __restrict__ pgrad, double inv_n,
+    int64_t total, int64_t C, int64_t HW, int W, int row_lo, int row_hi,
+    int col_lo, int col_hi) {
   constexpr int VEC = 16 / sizeof(T);
+  if (blockIdx.x == 0 && local != nullptr) {
+    // parameter gradients, one owner per element: the fp32 cast of the
+    // local sums, added into the gradient buffer or written to pgrad[2C]
+    for (int64_t ch = threadIdx.x; ch < C; ch += blockDim.x) {
+      const float b = (float)local[ch], w = (float)local[C + ch];
+      if (gb_acc != nullptr) gb_acc[ch] += b; else pgrad[ch] = b;
+      if (gw_acc != nullptr) gw_acc[ch] += w; else pgrad[C + ch] = w;
+    }
+  }
   const int64_t nvec = (total + VEC - 1) / VEC;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t iv = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; iv < nvec;
@@ -1392,8 +1414,8 @@ __global__ void bn_bwd_apply_kernel(
     if (WHOLE || (i + VEC <= total && rem + VEC <= HW)) {
       const int64_t ch = p0 % C;
       const float m = mean[ch], inv = invstd[ch], w = wgt[ch];
-      const float gsn = (float)(gsum[ch] * inv_n);
-      const float gxn = (float)(gxsum[ch] * inv_n);
+      const float gsn = bn_bwd_term(gsum[ch], inv_n);
+      const float gxn = bn_bwd_term(gxsum[ch], inv_n);
       int row = 0, col = 0;
       if (REGION) {
         row = (int)(rem / W);
@@ -1435,8 +1457,8 @@ __global__ void bn_bwd_apply_kernel(
           reduced = row >= row_lo && row < row_hi && col >= col_lo &&
                     col < col_hi;
         }
-        gi[k] = (T)bn_bwd_elem(g, xh, (float)(gsum[ch] * inv_n),
-                               (float)(gxsum[ch] * inv_n), wgt[ch], inv,
+        gi[k] = (T)bn_bwd_elem(g, xh, bn_bwd_term(gsum[ch], inv_n),
+                               bn_bwd_term(gxsum[ch], inv_n), wgt[ch], inv,
                                reduced);
       }
     }
@@ -1574,16 +1596,22 @@ void sgd_momentum(torch::Tensor p, torch::Tensor g, torch::Tensor v,
 
 // bn_finalize: fold the fp64 [sum,sumsq] -> [mean, invstd] conversion,
 // the running-stat EMA update and num_batches_tracked into ONE kernel
-// (the python glue cost ~8 small launches per BN call).
+// (the python glue cost ~8 small launches per BN call). `zero2`, when
+// given, is a second fp64 [2C] vector that is zero-filled on the way: the
+// accumulator of this forward's bn_bwd_stats.
 __global__ void bn_finalize_kernel(double* __restrict__ stats,
                                    float* __restrict__ out,
                                    float* __restrict__ rmean,
                                    float* __restrict__ rvar,
                                    int64_t* __restrict__ tracked, float mom,
                                    double n, float eps, int64_t C,
-                                   int rezero) {
+                                   int rezero, double* __restrict__ zero2) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= C) return;
+  if (zero2) {            // the backward statistics' accumulator of this
+    zero2[i] = 0.0;       // forward (bn_bwd_stats out): zeroed here, so the
+    zero2[C + i] = 0.0;   // backward launches no fill
+  }
   const double mean = stats[i] / n;
   double var = stats[C + i] / n - mean * mean;
   if (var < 0.0) var = 0.0;
@@ -1605,8 +1633,16 @@ torch::Tensor bn_finalize(torch::Tensor stats,
                           c10::optional<torch::Tensor> rmean,
                           c10::optional<torch::Tensor> rvar,
                           c10::optional<torch::Tensor> tracked, double mom,
-                          double n, double eps, bool rezero = false) {
+                          double n, double eps, bool rezero = false,
+                          c10::optional<torch::Tensor> zero2 = c10::nullopt) {
   const int64_t C = stats.numel() / 2;
+  if (zero2.has_value())
+    TORCH_CHECK(zero2->is_cuda() && zero2->is_contiguous() &&
+                    zero2->scalar_type() == torch::kDouble &&
+                    zero2->numel() == 2 * C &&
+                    zero2->get_device() == stats.get_device(),
+                "bn_finalize: zero2 must be a contiguous fp64 CUDA vector of "
+                "2*C on stats' device");
   auto out = torch::empty({2 * C}, stats.options().dtype(torch::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(
@@ -1615,7 +1651,8 @@ torch::Tensor bn_finalize(torch::Tensor stats,
       rmean.has_value() ? rmean->data_ptr<float>() : nullptr,
       rvar.has_value() ? rvar->data_ptr<float>() : nullptr,
       tracked.has_value() ? tracked->data_ptr<int64_t>() : nullptr,
-      (float)mom, n, (float)eps, C, rezero ? 1 : 0);
+      (float)mom, n, (float)eps, C, rezero ? 1 : 0,
+      zero2.has_value() ? zero2->data_ptr<double>() : nullptr);
   return out;
 }
 
@@ -2206,7 +2243,8 @@ torch::Tensor bn_apply(torch::Tensor x, torch::Tensor mean,
 
 torch::Tensor bn_bwd_stats(torch::Tensor go, torch::Tensor x, torch::Tensor y,
                            torch::Tensor mean, torch::Tensor invstd,
-                           bool relu) {
+                           bool relu,
+                           c10::optional<torch::Tensor> zeroed = c10::nullopt) {
   check_bn_x(x);
   const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   check_bn_like(go, x, "go");
@@ -2216,7 +2254,17 @@ torch::Tensor bn_bwd_stats(torch::Tensor go, torch::Tensor x, torch::Tensor y,
   go = slot_aligned(go);
   x = slot_aligned(x);
   if (relu) y = slot_aligned(y);
-  auto out = torch::zeros({2 * C}, x.options().dtype(torch::kDouble));
+  // `zeroed`: a caller-owned fp64 [2C] accumulator that holds zeros (the
+  // one bn_finalize zero-filled for this forward); else a fresh fill
+  torch::Tensor out;
+  if (zeroed.has_value()) {
+    out = *zeroed;
+    check_bn_out(out, C);
+    TORCH_CHECK(out.get_device() == x.get_device(),
+                "bn: out must be on x's device");
+  } else {
+    out = torch::zeros({2 * C}, x.options().dtype(torch::kDouble));
+  }
   const int64_t vec = 16 / (int64_t)x.element_size();
   const auto cg = stats_grid(C, HW, HW, slot_slack(vec, HW, 0));
   const int64_t chunk = cg.first, gy = cg.second;
@@ -2243,13 +2291,34 @@ torch::Tensor bn_bwd_stats(torch::Tensor go, torch::Tensor x, torch::Tensor y,
 // the launcher beneath bn_bwd_apply and bn_bwd_apply_region; `region`
 // restricts the two reduction terms to rows [row_lo,row_hi) x cols
 // [col_lo,col_hi)
+//
+// gsum / gxsum: the statistics as bn_bwd_stats made them (fp64, e.g. the
+// two halves of its result) or their fp32 cast; both give the same bits.
+// `pg` says where the launch puts the parameter gradients (none by default).
+struct BnParamGrads {
+  c10::optional<torch::Tensor> local;  // fp64 [2C]: this tile's own stats
+  c10::optional<torch::Tensor> gw, gb; // fp32 [C] each: added into in place
+  c10::optional<torch::Tensor> pgrad;  // fp32 [2C]: written where no gw/gb
+};
+
+static torch::Tensor bn_stat_f64(const torch::Tensor& v, int64_t C,
+                                 const char* name) {
+  TORCH_CHECK(v.is_cuda() && v.is_contiguous() && v.numel() == C &&
+                  (v.scalar_type() == torch::kFloat ||
+                   v.scalar_type() == torch::kDouble),
+              "bn: ", name, " must be a contiguous fp32 or fp64 CUDA vector "
+              "of ", C, " channels");
+  return v.scalar_type() == torch::kDouble ? v : v.to(torch::kDouble);
+}
+
 static torch::Tensor bn_bwd_apply_launch(torch::Tensor go, torch::Tensor x,
                                          torch::Tensor y, torch::Tensor mean,
                                          torch::Tensor invstd, torch::Tensor w,
                                          torch::Tensor gsum,
                                          torch::Tensor gxsum, double n,
                                          bool relu, bool region, int row_lo,
-                                         int row_hi, int col_lo, int col_hi) {
+                                         int row_hi, int col_lo, int col_hi,
+                                         const BnParamGrads& pg) {
   check_bn_x(x);
   const int64_t C = x.size(1), W = x.size(3), HW = x.size(2) * W;
   const int64_t total = x.numel();
@@ -2258,8 +2327,41 @@ static torch::Tensor bn_bwd_apply_launch(torch::Tensor go, torch::Tensor x,
   check_bn_vec(mean, C, "mean");
   check_bn_vec(invstd, C, "invstd");
   check_bn_vec(w, C, "w");
-  check_bn_vec(gsum, C, "gsum");
-  check_bn_vec(gxsum, C, "gxsum");
+  gsum = bn_stat_f64(gsum, C, "gsum");
+  gxsum = bn_stat_f64(gxsum, C, "gxsum");
+  const double* local = nullptr;
+  float *gw_acc = nullptr, *gb_acc = nullptr, *pgrad = nullptr;
+  auto here = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.get_device() == x.get_device() &&
+           t.is_contiguous();
+  };
+  if (pg.local.has_value()) {
+    check_bn_out(*pg.local, C);
+    TORCH_CHECK(here(*pg.local), "bn: local must be on x's device");
+    local = pg.local->data_ptr<double>();
+    auto sink = [&](const c10::optional<torch::Tensor>& t, const char* name) {
+      if (!t.has_value()) return (float*)nullptr;
+      TORCH_CHECK(here(*t) && t->scalar_type() == torch::kFloat &&
+                      t->numel() == C,
+                  "bn: ", name, " must be a contiguous fp32 vector of ", C,
+                  " channels on x's device");
+      return t->data_ptr<float>();
+    };
+    gw_acc = sink(pg.gw, "gw");
+    gb_acc = sink(pg.gb, "gb");
+    if (gw_acc == nullptr || gb_acc == nullptr) {
+      TORCH_CHECK(pg.pgrad.has_value() && here(*pg.pgrad) &&
+                      pg.pgrad->scalar_type() == torch::kFloat &&
+                      pg.pgrad->numel() == 2 * C,
+                  "bn: pgrad must be a contiguous fp32 vector of 2*C on x's "
+                  "device when gw or gb is not given");
+      pgrad = pg.pgrad->data_ptr<float>();
+    }
+  } else {
+    TORCH_CHECK(!pg.gw.has_value() && !pg.gb.has_value() &&
+                    !pg.pgrad.has_value(),
+                "bn: gw, gb and pgrad need local");
+  }
   go = slot_aligned(go);
   x = slot_aligned(x);
   if (relu) y = slot_aligned(y);
@@ -2282,8 +2384,9 @@ static torch::Tensor bn_bwd_apply_launch(torch::Tensor go, torch::Tensor x,
                   relu ? y.data_ptr<scalar_t>() : (scalar_t*)nullptr,
                   gi.data_ptr<scalar_t>(), mean.data_ptr<float>(),
                   invstd.data_ptr<float>(), w.data_ptr<float>(),
-                  gsum.data_ptr<float>(), gxsum.data_ptr<float>(), 1.0 / n,
-                  total, C, HW, (int)W, row_lo, row_hi, col_lo, col_hi);
+                  gsum.data_ptr<double>(), gxsum.data_ptr<double>(), local,
+                  gw_acc, gb_acc, pgrad, 1.0 / n, total, C, HW, (int)W, row_lo,
+                  row_hi, col_lo, col_hi);
             });
           });
         });
@@ -2294,9 +2397,13 @@ static torch::Tensor bn_bwd_apply_launch(torch::Tensor go, torch::Tensor x,
 torch::Tensor bn_bwd_apply(torch::Tensor go, torch::Tensor x, torch::Tensor y,
                            torch::Tensor mean, torch::Tensor invstd,
                            torch::Tensor w, torch::Tensor gsum,
-                           torch::Tensor gxsum, double n, bool relu) {
+                           torch::Tensor gxsum, double n, bool relu,
+                           c10::optional<torch::Tensor> local,
+                           c10::optional<torch::Tensor> gw,
+                           c10::optional<torch::Tensor> gb,
+                           c10::optional<torch::Tensor> pgrad) {
   return bn_bwd_apply_launch(go, x, y, mean, invstd, w, gsum, gxsum, n, relu,
-                             false, 0, 0, 0, 0);
+                             false, 0, 0, 0, 0, {local, gw, gb, pgrad});
 }
 
 // bn_bwd_apply when mean/var were taken over the region only
@@ -2306,14 +2413,19 @@ torch::Tensor bn_bwd_apply_region(torch::Tensor go, torch::Tensor x,
                                   torch::Tensor invstd, torch::Tensor w,
                                   torch::Tensor gsum, torch::Tensor gxsum,
                                   double n, bool relu,
-                                  std::vector<int64_t> margin) {
+                                  std::vector<int64_t> margin,
+                                  c10::optional<torch::Tensor> local,
+                                  c10::optional<torch::Tensor> gw,
+                                  c10::optional<torch::Tensor> gb,
+                                  c10::optional<torch::Tensor> pgrad) {
   check_bn_x(x);
   const int64_t H = x.size(2), W = x.size(3);
   check_margin(margin, H, W);
   const bool region = margin[0] + margin[1] + margin[2] + margin[3] != 0;
   return bn_bwd_apply_launch(go, x, y, mean, invstd, w, gsum, gxsum, n, relu,
                              region, (int)margin[0], (int)(H - margin[1]),
-                             (int)margin[2], (int)(W - margin[3]));
+                             (int)margin[2], (int)(W - margin[3]),
+                             {local, gw, gb, pgrad});
 }
 
 // ---------------- state fan binding ----------------
@@ -2430,20 +2542,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "avg_fwd, avg_bwd) launches; plain integers, no HIP call");
   m.def("bn_stats64", &bn_stats64);
   m.def("bn_apply", &bn_apply);
-  m.def("bn_bwd_stats", &bn_bwd_stats);
-  m.def("bn_bwd_apply", &bn_bwd_apply);
+  m.def("bn_bwd_stats", &bn_bwd_stats, py::arg("go"), py::arg("x"),
+        py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("relu"),
+        py::arg("out") = py::none(),
+        "fp64 [gsum, gxsum]; accumulated into `out` (zeroed, fp64 [2C]) when "
+        "given, so no fill is launched");
+  m.def("bn_bwd_apply", &bn_bwd_apply, py::arg("go"), py::arg("x"),
+        py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("w"),
+        py::arg("gsum"), py::arg("gxsum"), py::arg("n"), py::arg("relu"),
+        py::arg("local") = py::none(), py::arg("gw") = py::none(),
+        py::arg("gb") = py::none(), py::arg("pgrad") = py::none(),
+        "gi; with `local` (fp64 [2C]) the launch also adds the parameter "
+        "gradients into gw / gb, or writes them to pgrad (fp32 [2C])");
   m.def("sgd_momentum", &sgd_momentum);
   m.def("bn_finalize", &bn_finalize, pybind11::arg("stats"),
         pybind11::arg("rmean"), pybind11::arg("rvar"),
         pybind11::arg("tracked"), pybind11::arg("mom"), pybind11::arg("n"),
-        pybind11::arg("eps"), pybind11::arg("rezero") = false);
+        pybind11::arg("eps"), pybind11::arg("rezero") = false,
+        pybind11::arg("zero2") = pybind11::none());
   m.def("bn_stats64_acc", &bn_stats64_acc);
   m.def("bn_stats64_region_acc", &bn_stats64_region_acc, py::arg("x"),
         py::arg("out"), py::arg("margin"));
   m.def("bn_bwd_apply_region", &bn_bwd_apply_region, py::arg("go"),
         py::arg("x"), py::arg("y"), py::arg("mean"), py::arg("invstd"),
         py::arg("w"), py::arg("gsum"), py::arg("gxsum"), py::arg("n"),
-        py::arg("relu"), py::arg("margin"));
+        py::arg("relu"), py::arg("margin"), py::arg("local") = py::none(),
+        py::arg("gw") = py::none(), py::arg("gb") = py::none(),
+        py::arg("pgrad") = py::none());
   m.def("fan_bwd", &fan_bwd, py::arg("raw"), py::arg("rel"), py::arg("r"),
         py::arg("slot"),
         "gradient of a fanned-out state: ordered fold of raw and ReLU-masked "

@@ -53,3 +53,10 @@ def cell_glue_enabled() -> bool:
     torch.relu per consumer and autograd's pairwise gradient adds in the
     cells (ops/fuse.py). A cell reads it once per forward."""
     return os.environ.get("MPI4DL_CELL_GLUE", "1") != "0"
+
+
+def grad_sink_enabled() -> bool:
+    """MPI4DL_GRAD_SINK=0 restores, in the same build, weight gradients that
+    come back as tensors for autograd to add to p.grad (ops/grad_sink.py).
+    Read at every backward call."""
+    return os.environ.get("MPI4DL_GRAD_SINK", "1") != "0"

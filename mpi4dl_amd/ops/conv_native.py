@@ -38,6 +38,7 @@ import torch
 import torch.nn as nn
 
 from . import backend
+from .grad_sink import grad_sink
 
 _MIN_OW = 64
 _ONE_D_MIN_OW = 384
@@ -152,7 +153,13 @@ class ConvFn(torch.autograd.Function):
     """Executes ``conv_plan``. The plan is made once, in forward, and
     kept on ctx: backward does not read MPI4DL_PW_BLASLT again, so a
     change of the variable between a forward and its backward is
-    ignored."""
+    ignored.
+
+    Weight gradient: the routes that run our own kernels (pw_bwdw,
+    pw_bwdw_sub, conv_bwd_weight) add it straight into ``w.grad`` when
+    ``grad_sink(w)`` allows, and backward then returns None for ``w``;
+    otherwise, and on the bmm route, it is returned for autograd to
+    accumulate."""
 
     @staticmethod
     def forward(ctx, x, w, bias, sh, sw, ph, pw):
@@ -176,6 +183,7 @@ class ConvFn(torch.autograd.Function):
         ctx.wdtype = w.dtype
         ctx.has_bias = bias is not None
         ctx.plan = plan
+        ctx.wparam = w  # the Parameter itself: backward asks grad_sink(w)
         return y
 
     @staticmethod
@@ -194,13 +202,20 @@ class ConvFn(torch.autograd.Function):
                           xb.view(N, C, ohw).transpose(1, 2))
                 .float().sum(dim=0).view(K, C, 1, 1).to(ctx.wdtype)
             )
-        elif gw_route == "pw_bwdw":
-            gw = ge.pw_bwdw(go, xb).view(K, C, 1, 1).to(ctx.wdtype)
-        elif gw_route == "pw_bwdw_sub":
-            xs = xb[:, :, ::sh, ::sw].contiguous()
-            gw = ge.pw_bwdw(go, xs).view(K, C, 1, 1).to(ctx.wdtype)
         else:
-            gw = ge.conv_bwd_weight(go, xb, R, S, sh, sw, ph, pw).to(ctx.wdtype)
+            # our kernels finish with atomicAdd: with a sink they add into
+            # p.grad itself (no zero fill, no AccumulateGrad add) and the
+            # weight's gradient is returned as None
+            sink = grad_sink(ctx.wparam)
+            out = () if sink is None else (sink,)
+            if gw_route == "conv_bwd_weight":
+                gw = ge.conv_bwd_weight(go, xb, R, S, sh, sw, ph, pw, *out)
+            else:
+                xs = (xb if gw_route == "pw_bwdw"
+                      else xb[:, :, ::sh, ::sw].contiguous())
+                gw = ge.pw_bwdw(go, xs, *out)
+            gw = None if sink is not None else (
+                gw.view(K, C, R, S).to(ctx.wdtype))
         gb = go.sum(dim=(0, 2, 3)).to(ctx.wdtype) if ctx.has_bias else None
         if not ctx.needs_input_grad[0]:
             # first layer: the input is data — skip the whole gx leg

@@ -4,6 +4,10 @@ Each Function pairs a hand-written HIP forward with its hand-written
 backward (no eager fallback on GPU — backend.py raises if the extension
 is missing). CPU paths never reach these; the modules in
 ops/spatial_conv.py and ops/norm.py dispatch here only for CUDA inputs.
+
+BatchNormFn hands its parameter gradients to the gradient sink
+(ops/grad_sink.py): where allowed, the backward kernel adds them into
+``weight.grad`` / ``bias.grad`` itself and autograd gets None.
 """
 
 from __future__ import annotations
@@ -12,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from . import backend
+from .grad_sink import grad_sink
 
 
 def _plane_dense(go):
@@ -87,11 +92,21 @@ class BatchNormFn(torch.autograd.Function):
     the region inside the margin only (n_global counts region pixels):
     the gsum/gxsum sums still run over every pixel, but their terms
     reach region pixels only (bn_bwd_apply_region).
+
+    ``bwd_stats``: an fp64 [2C] buffer that holds zeros (bn_finalize
+    zero-filled it for this forward); the first backward accumulates its
+    statistics there instead of filling a fresh one.
+
+    The parameter gradients are the fp32 cast of the LOCAL statistics.
+    Block 0 of the bn_bwd_apply launch makes them: added in place into
+    weight.grad / bias.grad where ``grad_sink`` allows (the Function then
+    returns None for that parameter), else written to a fresh tensor that
+    is returned. No cast kernel runs either way.
     """
 
     @staticmethod
     def forward(ctx, x, weight, bias, mean, invstd, group, n_global, training,
-                relu, margin=(0, 0, 0, 0)):
+                relu, margin=(0, 0, 0, 0), bwd_stats=None):
         ge = backend.ext()
         x = x.contiguous()
         w32 = weight.detach().float().contiguous()
@@ -104,6 +119,8 @@ class BatchNormFn(torch.autograd.Function):
         ctx.training = training
         ctx.relu = relu
         ctx.margin = tuple(margin) if training else (0, 0, 0, 0)
+        ctx.params = (weight, bias)  # the Parameters: backward asks grad_sink
+        ctx.bwd_stats = bwd_stats    # zeroed; handed out once (backward)
         return y
 
     @staticmethod
@@ -112,42 +129,53 @@ class BatchNormFn(torch.autograd.Function):
         x, y, mean, invstd, w32 = ctx.saved_tensors
         go = go.contiguous()
         C = x.shape[1]
-        stats = ge.bn_bwd_stats(go, x, y, mean, invstd, ctx.relu)  # fp64
-        sf = stats.float()  # ONE cast; gw/gb are views of it
-        gw = sf[C:]  # local sum(go*xhat)
-        gb = sf[:C]  # local sum(go)
+        # the zeroed buffer serves one backward: after it the buffer is
+        # dirty, and a second backward over a retained graph fills its own
+        zeroed, ctx.bwd_stats = ctx.bwd_stats, None
+        stats = ge.bn_bwd_stats(go, x, y, mean, invstd, ctx.relu,
+                                out=zeroed)  # fp64 [gsum, gxsum], local
+        gw_sink, gb_sink = (grad_sink(p) for p in ctx.params)
+        pgrad = None
+        if gw_sink is None or gb_sink is None:
+            pgrad = torch.empty(2 * C, device=x.device, dtype=torch.float32)
+        param_grads = dict(
+            local=stats,
+            gw=None if gw_sink is None else gw_sink.view(-1),
+            gb=None if gb_sink is None else gb_sink.view(-1),
+            pgrad=pgrad,
+        )
         if ctx.training:
             if ctx.group is not None:
                 g_global = stats.clone()
                 dist.all_reduce(g_global, group=ctx.group)
-                gf = g_global.float()
             else:
-                gf = sf
+                g_global = stats
             if any(ctx.margin):
                 gi = ge.bn_bwd_apply_region(
-                    go, x, y, mean, invstd, w32,
-                    gf[:C].contiguous(), gf[C:].contiguous(),
+                    go, x, y, mean, invstd, w32, g_global[:C], g_global[C:],
                     float(ctx.n_global), ctx.relu, list(ctx.margin),
+                    **param_grads,
                 )
             else:
                 gi = ge.bn_bwd_apply(
-                    go, x, y, mean, invstd, w32,
-                    gf[:C].contiguous(), gf[C:].contiguous(),
-                    float(ctx.n_global), ctx.relu,
+                    go, x, y, mean, invstd, w32, g_global[:C], g_global[C:],
+                    float(ctx.n_global), ctx.relu, **param_grads,
                 )
         else:
             # eval: mean/var are constants -> gi = go_eff * w * invstd
-            zeros = torch.zeros(2 * C, device=x.device, dtype=torch.float32)
+            zeros = torch.zeros(2 * C, device=x.device, dtype=torch.float64)
             gi = ge.bn_bwd_apply(
-                go, x, y, mean, invstd, w32,
-                zeros[:C].contiguous(), zeros[C:].contiguous(),
-                1.0, ctx.relu,
+                go, x, y, mean, invstd, w32, zeros[:C], zeros[C:],
+                1.0, ctx.relu, **param_grads,
             )
-        return (gi, gw.to(ctx.wdtype), gb.to(ctx.wdtype)) + (None,) * 7
+        gw = None if gw_sink is not None else pgrad[C:].to(ctx.wdtype)
+        gb = None if gb_sink is not None else pgrad[:C].to(ctx.wdtype)
+        return (gi, gw, gb) + (None,) * 8
 
 
 def native_batchnorm(x, weight, bias, mean, invstd, group, n_global, training,
-                     relu=False, margin=(0, 0, 0, 0)):
+                     relu=False, margin=(0, 0, 0, 0), bwd_stats=None):
     return BatchNormFn.apply(
-        x, weight, bias, mean, invstd, group, n_global, training, relu, margin
+        x, weight, bias, mean, invstd, group, n_global, training, relu, margin,
+        bwd_stats,
     )

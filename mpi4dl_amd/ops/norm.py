@@ -162,18 +162,23 @@ class TileBatchNorm2d(nn.BatchNorm2d):
                 dist.all_reduce(stats, group=group)
                 n *= dist.get_world_size(group=group)
             m = self.momentum if self.momentum is not None else 0.1
+            # the accumulator of this call's backward statistics: per call
+            # (backwards of several micro-batches may be pending at once),
+            # zero-filled by bn_finalize, so backward launches no fill
+            bwd_stats = torch.empty(2 * C, device=x.device, dtype=torch.float64)
             mv = ge.bn_finalize(
                 stats,
                 self.running_mean if self.track_running_stats else None,
                 self.running_var if self.track_running_stats else None,
                 self.num_batches_tracked if self.track_running_stats else None,
-                m, float(n), self.eps, rezero=True,
+                m, float(n), self.eps, rezero=True, zero2=bwd_stats,
             )
             mean, invstd = mv[:C], mv[C:]
         else:
+            bwd_stats = None
             mean = self.running_mean.float().contiguous()
             invstd = torch.rsqrt(self.running_var.float() + self.eps).contiguous()
         return native_batchnorm(
             x, self.weight, self.bias, mean.contiguous(), invstd.contiguous(),
-            group, float(n), self.training, self.relu, mg,
+            group, float(n), self.training, self.relu, mg, bwd_stats,
         )

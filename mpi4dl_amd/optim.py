@@ -5,7 +5,10 @@ per step (torch SGD iterates parameters). Here the model's parameters
 and gradients live as views into single flat fp32 buffers (grads via
 comm.FlatGrads — shared with GradReducer so collectives stay single
 messages), plus one flat momentum buffer; step() is ONE
-gemscore.sgd_momentum launch that also zeroes the grads.
+gemscore.sgd_momentum launch that also zeroes the grads. That zeroed
+buffer is what the weight-gradient kernels of the next backward add
+into directly (ops/grad_sink.py); autograd's AccumulateGrad adds only
+the gradients that come back as tensors.
 
 CPU fallback implements the same math with three tensor ops.
 """
