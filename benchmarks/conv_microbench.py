@@ -38,32 +38,50 @@ def timeit(fn, iters, warmup=5):
     return (time.perf_counter() - t0) / iters * 1e3
 
 
+# ResNet's stride-1 3x3 stack (C = K, H = W), all at pad 1
+WINO_SHAPES = [(64, 512), (128, 256), (256, 128), (512, 64), (416, 256)]
+
+
 def winograd_ab(args):
-    """F(2x2,3x3) batched-GEMM staging vs MIOpen at the bench 3x3 shapes."""
+    """Stride-1 3x3: the fused F(2x2,3x3) kernel (ge.wino_fwd), the
+    batched-GEMM staging, our direct v2<3,*> kernel (ge.conv_fwd) and
+    MIOpen. All four are warmed up first; the timed rounds then alternate
+    between them, and the median round of each is reported. Ratios are
+    MIOpen's time over the variant's (above 1: the variant is faster)."""
+    from mpi4dl_amd.ops import backend
     from mpi4dl_amd.ops.winograd_ref import filter_transform, winograd_bmm_conv2d
 
-    print(f"{'shape':<42} {'winograd':>9} {'miopen':>9} {'ratio':>6}")
-    for C, K, H, W, kh, kw, s, ph, pw in SHAPES:
-        if (kh, kw) != (3, 3) or s != 1:
-            continue
-        x = torch.randn(args.batch, C, H, W, device="cuda", dtype=torch.bfloat16)
-        w = torch.randn(K, C, 3, 3, device="cuda") * 0.05
+    ge = backend.ext()
+    names = ("fused", "staging", "direct", "miopen")
+    print(f"{'shape':<26}" + "".join(f"{n:>11}" for n in names)
+          + "   fused/staging/direct vs miopen")
+    for C, hw in WINO_SHAPES:
+        x = torch.randn(args.batch, C, hw, hw, device="cuda", dtype=torch.bfloat16)
+        w = torch.randn(C, C, 3, 3, device="cuda") * 0.05
+        wb = w.to(torch.bfloat16)
         U = filter_transform(w)
-        tw = timeit(lambda: winograd_bmm_conv2d(x, U, None, padding=ph),
-                    args.iters)
-        tm = timeit(
-            lambda: torch.nn.functional.conv2d(
-                x, w.to(torch.bfloat16), stride=1, padding=(ph, pw)
-            ),
-            args.iters,
-        )
-        y = winograd_bmm_conv2d(x, U, None, padding=ph)
-        ref = torch.nn.functional.conv2d(
-            x.float(), w, stride=1, padding=(ph, pw)
-        )
-        rel = (y - ref).abs().max().item() / max(ref.abs().max().item(), 1e-3)
-        tag = f"C{C}->K{K} {H}x{W} k3x3"
-        print(f"{tag:<42} {tw:8.3f}ms {tm:8.3f}ms {tm/tw:5.2f}x  relerr {rel:.3g}")
+        fns = {
+            "fused": lambda: ge.wino_fwd(x, wb, None, 1, 1),
+            "staging": lambda: winograd_bmm_conv2d(x, U, None, padding=1),
+            "direct": lambda: ge.conv_fwd(x, wb, None, 1, 1, 1, 1),
+            "miopen": lambda: torch.nn.functional.conv2d(x, wb, padding=1),
+        }
+        for fn in fns.values():
+            timeit(fn, 2, warmup=3)
+        rounds = {n: [] for n in names}
+        for _ in range(5):
+            for n in names:
+                rounds[n].append(timeit(fns[n], max(args.iters // 5, 2), warmup=0))
+        t = {n: sorted(v)[len(v) // 2] for n, v in rounds.items()}
+        ref = torch.nn.functional.conv2d(x.float(), wb.float(), padding=1)
+        rel = ((fns["fused"]().float() - ref).abs().max().item()
+               / max(ref.abs().max().item(), 1e-3))
+        tag = f"C{C}->K{C} {hw}x{hw} N{args.batch}"
+        print(f"{tag:<26}" + "".join(f"{t[n]:9.3f}ms" for n in names)
+              + "   " + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:3])
+              + f"  [{ge.wino_kernel_name(C, C, hw, hw, 1, 1)}, "
+              f"{ge.conv_fwd_kernel_name(C, C, hw, hw, 3, 3, 1, 1, 1, 1)}]"
+              f"  fused relerr {rel:.3g}", flush=True)
 
 
 def model_pw_shapes(num_layers=18, num_filters=416, image=2048, mb=2):
@@ -236,8 +254,9 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--winograd", action="store_true",
-                    help="A/B winograd_bmm_conv2d vs MIOpen on the 3x3 "
-                         "stride-1 shapes (round-2 staging)")
+                    help="A/B the fused Winograd kernel, the bmm staging and "
+                         "the direct kernel vs MIOpen on the 3x3 stride-1 "
+                         "shapes")
     ap.add_argument("--pw", action="store_true",
                     help="A/B the conv_pw 1x1 kernel vs MIOpen on the "
                          "flagship model's 1x1 shapes")

@@ -11,6 +11,14 @@ Kernel families (csrc/):
   (pw_fat_kernel<4|8>), stride-2 gather + scatter backward-data, and
   the NT-GEMM bwd-weight with pixel-slab split-K at the same two
   tiles (pw_bwdw_kernel<4|8>).
+* conv_wino.hip — fused Winograd F(2x2,3x3) for stride-1 3x3 (any pad in
+  {0,1,2}, any N, C, K, H, W): filter transform to bf16 U, then one
+  launch with the input transform, the 16 MFMA GEMMs and the output
+  transform; its data-grad is the same kernel on the output gradient
+  with the filter transform reading the forward weight transposed and
+  rotated. Opt-in: MPI4DL_WINOGRAD=fused routes the forward and
+  data-grad legs of every supported 3x3 there (weight-grad stays on
+  conv_bwd_weight). The default dispatch does not use it yet.
 
 Per-shape, per-LEG policy (all crossovers measured on MI355X —
 profiles/PERF_NOTES.md): stride-2 1x1s, K<=64 1x1s, stems, wide
@@ -22,11 +30,12 @@ F.conv2d/MIOpen. MPI4DL_NATIVE_CONV=0 disables all native paths,
 =1 forces them (A/B benchmarking).
 
 The per-leg policy is written once, in ``conv_plan``: a pure function
-of the problem's integers and the MPI4DL_PW_BLASLT switch. ``ConvFn``
+of the problem's integers and the MPI4DL_PW_BLASLT and
+MPI4DL_WINOGRAD=fused switches. ``ConvFn``
 executes the plan and decides nothing itself; which kernel a native
 route then launches is the extension's choice (``conv_fwd_kernel_name``,
-``pw_kernel_name``, ``pw_bwdw_kernel_name`` answer it for a plan's
-problems).
+``pw_kernel_name``, ``pw_bwdw_kernel_name``, ``wino_kernel_name`` answer
+it for a plan's problems).
 """
 
 from __future__ import annotations
@@ -66,6 +75,19 @@ def _blaslt_on():
     return os.environ.get("MPI4DL_PW_BLASLT", "1") != "0"
 
 
+def _wino_fused_on():
+    return os.environ.get("MPI4DL_WINOGRAD", "0") == "fused"
+
+
+def _wino_ok(H, W, R, S, sh, sw, ph, pw):
+    """What conv_wino.hip serves: 3x3, stride 1, pads in {0, 1, 2}, at
+    least one output pixel (dilation 1 and groups 1 are the caller's)."""
+    return (
+        (R, S, sh, sw) == (3, 3, 1, 1) and ph in (0, 1, 2) and pw in (0, 1, 2)
+        and H + 2 * ph >= 3 and W + 2 * pw >= 3
+    )
+
+
 class Leg(NamedTuple):
     """How one of y, gx, gw is computed.
 
@@ -81,6 +103,10 @@ class Leg(NamedTuple):
                              (C, K, H, W, R, S, sh, sw, ph, pw)
       conv_bwd_weight        ge.conv_bwd_weight; problem = the forward
                              convolution's, as for conv_fwd
+      wino_fwd               ge.wino_fwd (for gx: transposed, on the output
+                             gradient); problem = wino_kernel_name's
+                             (C, K, H, W, ph, pw): C the reduction dim and
+                             K the output channels of the launch
     """
 
     route: str
@@ -93,12 +119,16 @@ class ConvPlan(NamedTuple):
     gw: Leg
 
 
-def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None):
+def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
+              winograd=None):
     """The route of each leg of the convolution x[N,C,H,W] * w[K,C,R,S]
     and the problem that route hands to its binding. ``blaslt`` defaults
-    to the MPI4DL_PW_BLASLT switch; nothing else is read."""
+    to the MPI4DL_PW_BLASLT switch and ``winograd`` to
+    MPI4DL_WINOGRAD == "fused"; nothing else is read."""
     if blaslt is None:
         blaslt = _blaslt_on()
+    if winograd is None:
+        winograd = _wino_fused_on()
     OH = (H + 2 * ph - R) // sh + 1
     OW = (W + 2 * pw - S) // sw + 1
     ohw = OH * OW
@@ -133,6 +163,14 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None):
               else Leg("pw_bwdw", (N, K, C, ohw)))
         return ConvPlan(y, gx, gw)
     fwd = (C, K, H, W, R, S, sh, sw, ph, pw)
+    if winograd and _wino_ok(H, W, R, S, sh, sw, ph, pw):
+        # opt-in fused Winograd: forward, and the data-grad as the same
+        # kernel on go with pads 2-p; the weight-grad keeps its kernel
+        return ConvPlan(
+            Leg("wino_fwd", (C, K, H, W, ph, pw)),
+            Leg("wino_fwd", (K, C, OH, OW, 2 - ph, 2 - pw)),
+            Leg("conv_bwd_weight", fwd),
+        )
     if (sh, sw) == (1, 1):
         # stride-1 data-grad = the forward kernel on C<->K transposed,
         # 180-rotated weights
@@ -151,9 +189,9 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None):
 
 class ConvFn(torch.autograd.Function):
     """Executes ``conv_plan``. The plan is made once, in forward, and
-    kept on ctx: backward does not read MPI4DL_PW_BLASLT again, so a
-    change of the variable between a forward and its backward is
-    ignored.
+    kept on ctx: backward reads neither MPI4DL_PW_BLASLT nor
+    MPI4DL_WINOGRAD again, so a change of a variable between a forward
+    and its backward is ignored.
 
     Weight gradient: the routes that run our own kernels (pw_bwdw,
     pw_bwdw_sub, conv_bwd_weight) add it straight into ``w.grad`` when
@@ -176,6 +214,8 @@ class ConvFn(torch.autograd.Function):
             y = y.view(N, K, H, W)
         elif plan.y.route == "pw_fwd":
             y = ge.pw_fwd(xb, wb, bias, sh, sw)
+        elif plan.y.route == "wino_fwd":
+            y = ge.wino_fwd(xb, wb, bias, ph, pw)
         else:
             y = ge.conv_fwd(xb, wb, bias, sh, sw, ph, pw)
         ctx.save_for_backward(xb, wb)
@@ -232,6 +272,9 @@ class ConvFn(torch.autograd.Function):
         elif gx_route == "pw_bwd_data_strided":
             wt = wb.view(K, C).t().contiguous()
             gx = ge.pw_bwd_data_strided(go, wt, H, W, sh, sw)
+        elif gx_route == "wino_fwd":
+            # the filter transform reads wb transposed and rotated itself
+            gx = ge.wino_fwd(go, wb, None, 2 - ph, 2 - pw, True)
         else:
             # conv_fwd on go, or on go zero-stuffed to the plan's extents
             _, _, hs, ws, _, _, _, _, tph, tpw = ctx.plan.gx.problem
@@ -289,11 +332,30 @@ def _dispatchable(x, conv: nn.Conv2d) -> bool:
     return one_d and ow >= _ONE_D_MIN_OW and x.shape[1] <= 256
 
 
+def _wino_dispatchable(x, conv: nn.Conv2d) -> bool:
+    """MPI4DL_WINOGRAD=fused: a supported 3x3 on a CUDA tensor, under
+    the bf16/autocast condition of ``_dispatchable``."""
+    if not _wino_fused_on():
+        return False
+    if not (x.is_cuda and not x.is_meta) or x.dim() != 4:
+        return False
+    if conv.groups != 1 or _pair(conv.dilation) != (1, 1):
+        return False
+    if not (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()):
+        return False
+    if isinstance(conv.padding, str) or conv.padding_mode != "zeros":
+        return False
+    return _wino_ok(x.shape[-2], x.shape[-1], *_pair(conv.kernel_size),
+                    *_pair(conv.stride), *_pair(conv.padding))
+
+
 class NativeConv2d(nn.Conv2d):
     """nn.Conv2d that runs on the gemscore implicit-GEMM MFMA kernels
     when dispatchable (state-dict compatible with nn.Conv2d)."""
 
     def forward(self, x):
+        if _wino_dispatchable(x, self):
+            return native_conv2d(x, self.weight, self.bias, self.stride, self.padding)
         if (
             os.environ.get("MPI4DL_WINOGRAD", "0") == "1"
             and self.kernel_size == (3, 3)

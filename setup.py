@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "mpi4dl_amd/csrc/gemscore.hip",
         "mpi4dl_amd/csrc/conv_mfma.hip",
         "mpi4dl_amd/csrc/conv_pw.hip",
+        "mpi4dl_amd/csrc/conv_wino.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
