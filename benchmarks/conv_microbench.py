@@ -84,6 +84,74 @@ def winograd_ab(args):
               f"  fused relerr {rel:.3g}", flush=True)
 
 
+# (C = K, H = W, R, S) at stride 1, "same" padding: AmoebaNet's
+# conv_1x7_7x1 legs per plane, then ResNet's 3x3 stack
+TAP_SHAPES = (
+    [(c, hw, r, s) for c, hw in ((104, 256), (208, 128), (416, 64), (52, 512))
+     for r, s in ((1, 7), (7, 1))]
+    + [(c, hw, 3, 3) for c, hw in WINO_SHAPES[:4]]
+)
+
+
+def tap_ab(args):
+    """Stride-1 1x7 / 7x1 / 3x3, forward and data-grad legs: the tap-shift
+    kernel (ge.tap_fwd, filter pre-pass included), our direct kernel
+    (ge.conv_fwd; its data-grad includes the weight transpose and flip that
+    ConvFn does) and MIOpen. All variants are warmed up first; the timed
+    rounds then alternate between them, and the median round of each is
+    reported. Ratios are MIOpen's time over the variant's."""
+    import torch.nn.functional as F
+
+    from mpi4dl_amd.ops import backend
+
+    ge = backend.ext()
+    names = ("tap", "direct", "miopen")
+    print(f"{'shape':<34}{'leg':<5}" + "".join(f"{n:>11}" for n in names)
+          + "   tap/direct vs miopen  winner")
+    for C, hw, R, S in TAP_SHAPES:
+        ph, pw = R // 2, S // 2
+        N = args.batch
+        x = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
+        go = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
+        wb = (torch.randn(C, C, R, S, device="cuda") * 0.05).to(torch.bfloat16)
+        legs = {
+            "fwd": {
+                "tap": lambda: ge.tap_fwd(x, wb, None, ph, pw),
+                "direct": lambda: ge.conv_fwd(x, wb, None, 1, 1, ph, pw),
+                "miopen": lambda: F.conv2d(x, wb, padding=(ph, pw)),
+            },
+            "gx": {
+                "tap": lambda: ge.tap_fwd(go, wb, None, R - 1 - ph,
+                                          S - 1 - pw, True),
+                "direct": lambda: ge.conv_fwd(
+                    go, wb.transpose(0, 1).flip(2, 3).contiguous(), None,
+                    1, 1, R - 1 - ph, S - 1 - pw),
+                "miopen": lambda: torch.nn.grad.conv2d_input(
+                    x.shape, wb, go, padding=(ph, pw)),
+            },
+        }
+        for leg, fns in legs.items():
+            for fn in fns.values():
+                timeit(fn, 2, warmup=3)
+            rounds = {n: [] for n in names}
+            for _ in range(5):
+                for n in names:
+                    rounds[n].append(
+                        timeit(fns[n], max(args.iters // 5, 2), warmup=0))
+            t = {n: sorted(v)[len(v) // 2] for n, v in rounds.items()}
+            ref = fns["miopen"]().float()
+            rel = ((fns["tap"]().float() - ref).abs().max().item()
+                   / max(ref.abs().max().item(), 1e-3))
+            tag = f"C{C}->K{C} {hw}x{hw} k{R}x{S} N{N}"
+            print(f"{tag:<34}{leg:<5}"
+                  + "".join(f"{t[n]:9.3f}ms" for n in names) + "   "
+                  + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:2])
+                  + f"  {min(t, key=t.get):<7}"
+                  f"[{ge.tap_kernel_name(C, C, hw, hw, R, S, ph, pw)}, "
+                  f"{ge.conv_fwd_kernel_name(C, C, hw, hw, R, S, 1, 1, ph, pw)}]"
+                  f"  tap relerr {rel:.3g}", flush=True)
+
+
 def model_pw_shapes(num_layers=18, num_filters=416, image=2048, mb=2):
     """Every distinct 1x1 conv shape the flagship model runs (meta pass)."""
     from mpi4dl_amd.models.amoebanet import amoebanetd
@@ -257,6 +325,10 @@ def main():
                     help="A/B the fused Winograd kernel, the bmm staging and "
                          "the direct kernel vs MIOpen on the 3x3 stride-1 "
                          "shapes")
+    ap.add_argument("--tap", action="store_true",
+                    help="A/B the tap-shift kernel and the direct kernel vs "
+                         "MIOpen on the stride-1 1x7, 7x1 and 3x3 shapes, "
+                         "forward and data-grad")
     ap.add_argument("--pw", action="store_true",
                     help="A/B the conv_pw 1x1 kernel vs MIOpen on the "
                          "flagship model's 1x1 shapes")
@@ -269,6 +341,8 @@ def main():
         return matmul_ab(args)
     if args.winograd:
         return winograd_ab(args)
+    if args.tap:
+        return tap_ab(args)
     if args.pw:
         return pw_ab(args)
     if args.bwdw:

@@ -2513,10 +2513,12 @@ torch::Tensor fan_bwd(std::vector<torch::Tensor> raw,
 void register_conv_mfma(pybind11::module_& m);
 void register_conv_wino(pybind11::module_& m);
 void register_conv_pw(pybind11::module_& m);
+void register_conv_tap(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_conv_mfma(m);
   register_conv_wino(m);
+  register_conv_tap(m);
   register_conv_pw(m);
   m.def("halo_pack", &halo_copy<0>, "pack halo strips tile->flat buffer");
   m.def("halo_unpack", &halo_copy<1>, "unpack halo strips buffer->tile");

@@ -19,6 +19,19 @@ Kernel families (csrc/):
   rotated. Opt-in: MPI4DL_WINOGRAD=fused routes the forward and
   data-grad legs of every supported 3x3 there (weight-grad stays on
   conv_bwd_weight). The default dispatch does not use it yet.
+* conv_tap.hip — tap-shift direct conv for stride-1 1x7, 7x1 and 3x3 (pads
+  0..R-1 x 0..S-1, any N, C, K, H, W): a filter pre-pass to Wt[R*S][Kp][Cp],
+  then one launch that stages each 32-channel input patch into LDS once,
+  channel-innermost, and takes every tap as an address offset into it; its
+  data-grad is the same kernel on the output gradient with the pre-pass
+  reading the forward weight transposed and rotated. Opt-in:
+  MPI4DL_TAPCONV=1 routes the forward and data-grad legs of every
+  supported problem there (weight-grad stays on conv_bwd_weight; a 3x3
+  stays on Winograd when MPI4DL_WINOGRAD=fused is set too). Measured
+  (PERF_NOTES, "Tap-shift conv"): both legs beat MIOpen at the 512²,
+  256² and 128² planes and lose at 64²; the switch as a whole is 0.89x
+  end to end because of the weight-grad leg. The default dispatch does
+  not use it.
 
 Per-shape, per-LEG policy (all crossovers measured on MI355X —
 profiles/PERF_NOTES.md): stride-2 1x1s, K<=64 1x1s, stems, wide
@@ -30,12 +43,12 @@ F.conv2d/MIOpen. MPI4DL_NATIVE_CONV=0 disables all native paths,
 =1 forces them (A/B benchmarking).
 
 The per-leg policy is written once, in ``conv_plan``: a pure function
-of the problem's integers and the MPI4DL_PW_BLASLT and
-MPI4DL_WINOGRAD=fused switches. ``ConvFn``
+of the problem's integers and the MPI4DL_PW_BLASLT,
+MPI4DL_WINOGRAD=fused and MPI4DL_TAPCONV=1 switches. ``ConvFn``
 executes the plan and decides nothing itself; which kernel a native
 route then launches is the extension's choice (``conv_fwd_kernel_name``,
-``pw_kernel_name``, ``pw_bwdw_kernel_name``, ``wino_kernel_name`` answer
-it for a plan's problems).
+``pw_kernel_name``, ``pw_bwdw_kernel_name``, ``wino_kernel_name``,
+``tap_kernel_name`` answer it for a plan's problems).
 """
 
 from __future__ import annotations
@@ -88,6 +101,21 @@ def _wino_ok(H, W, R, S, sh, sw, ph, pw):
     )
 
 
+def _tap_on():
+    return os.environ.get("MPI4DL_TAPCONV", "0") == "1"
+
+
+def _tap_ok(H, W, R, S, sh, sw, ph, pw):
+    """What conv_tap.hip serves: 1x7, 7x1 or 3x3, stride 1, pads in
+    [0, R-1] x [0, S-1], at least one output pixel (dilation 1 and groups
+    1 are the caller's)."""
+    return (
+        (R, S) in ((1, 7), (7, 1), (3, 3)) and (sh, sw) == (1, 1)
+        and 0 <= ph <= R - 1 and 0 <= pw <= S - 1
+        and H + 2 * ph >= R and W + 2 * pw >= S
+    )
+
+
 class Leg(NamedTuple):
     """How one of y, gx, gw is computed.
 
@@ -107,6 +135,10 @@ class Leg(NamedTuple):
                              gradient); problem = wino_kernel_name's
                              (C, K, H, W, ph, pw): C the reduction dim and
                              K the output channels of the launch
+      tap_fwd                ge.tap_fwd (for gx: transposed, on the output
+                             gradient); problem = tap_kernel_name's
+                             (C, K, H, W, R, S, ph, pw), C and K as for
+                             wino_fwd
     """
 
     route: str
@@ -120,15 +152,18 @@ class ConvPlan(NamedTuple):
 
 
 def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
-              winograd=None):
+              winograd=None, tap=None):
     """The route of each leg of the convolution x[N,C,H,W] * w[K,C,R,S]
     and the problem that route hands to its binding. ``blaslt`` defaults
-    to the MPI4DL_PW_BLASLT switch and ``winograd`` to
-    MPI4DL_WINOGRAD == "fused"; nothing else is read."""
+    to the MPI4DL_PW_BLASLT switch, ``winograd`` to
+    MPI4DL_WINOGRAD == "fused" and ``tap`` to MPI4DL_TAPCONV == "1";
+    nothing else is read."""
     if blaslt is None:
         blaslt = _blaslt_on()
     if winograd is None:
         winograd = _wino_fused_on()
+    if tap is None:
+        tap = _tap_on()
     OH = (H + 2 * ph - R) // sh + 1
     OW = (W + 2 * pw - S) // sw + 1
     ohw = OH * OW
@@ -171,6 +206,15 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
             Leg("wino_fwd", (K, C, OH, OW, 2 - ph, 2 - pw)),
             Leg("conv_bwd_weight", fwd),
         )
+    if tap and _tap_ok(H, W, R, S, sh, sw, ph, pw):
+        # opt-in tap-shift kernel: forward, and the data-grad as the same
+        # kernel on go with the complementary pads; the weight-grad keeps
+        # its kernel
+        return ConvPlan(
+            Leg("tap_fwd", (C, K, H, W, R, S, ph, pw)),
+            Leg("tap_fwd", (K, C, OH, OW, R, S, R - 1 - ph, S - 1 - pw)),
+            Leg("conv_bwd_weight", fwd),
+        )
     if (sh, sw) == (1, 1):
         # stride-1 data-grad = the forward kernel on C<->K transposed,
         # 180-rotated weights
@@ -189,9 +233,9 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
 
 class ConvFn(torch.autograd.Function):
     """Executes ``conv_plan``. The plan is made once, in forward, and
-    kept on ctx: backward reads neither MPI4DL_PW_BLASLT nor
-    MPI4DL_WINOGRAD again, so a change of a variable between a forward
-    and its backward is ignored.
+    kept on ctx: backward reads none of MPI4DL_PW_BLASLT,
+    MPI4DL_WINOGRAD and MPI4DL_TAPCONV again, so a change of a variable
+    between a forward and its backward is ignored.
 
     Weight gradient: the routes that run our own kernels (pw_bwdw,
     pw_bwdw_sub, conv_bwd_weight) add it straight into ``w.grad`` when
@@ -216,6 +260,8 @@ class ConvFn(torch.autograd.Function):
             y = ge.pw_fwd(xb, wb, bias, sh, sw)
         elif plan.y.route == "wino_fwd":
             y = ge.wino_fwd(xb, wb, bias, ph, pw)
+        elif plan.y.route == "tap_fwd":
+            y = ge.tap_fwd(xb, wb, bias, ph, pw)
         else:
             y = ge.conv_fwd(xb, wb, bias, sh, sw, ph, pw)
         ctx.save_for_backward(xb, wb)
@@ -275,6 +321,9 @@ class ConvFn(torch.autograd.Function):
         elif gx_route == "wino_fwd":
             # the filter transform reads wb transposed and rotated itself
             gx = ge.wino_fwd(go, wb, None, 2 - ph, 2 - pw, True)
+        elif gx_route == "tap_fwd":
+            # the filter pre-pass reads wb transposed and rotated itself
+            gx = ge.tap_fwd(go, wb, None, R - 1 - ph, S - 1 - pw, True)
         else:
             # conv_fwd on go, or on go zero-stuffed to the plan's extents
             _, _, hs, ws, _, _, _, _, tph, tpw = ctx.plan.gx.problem
@@ -349,12 +398,29 @@ def _wino_dispatchable(x, conv: nn.Conv2d) -> bool:
                     *_pair(conv.stride), *_pair(conv.padding))
 
 
+def _tap_dispatchable(x, conv: nn.Conv2d) -> bool:
+    """MPI4DL_TAPCONV=1: a supported 1x7, 7x1 or 3x3 on a CUDA tensor,
+    under the bf16/autocast condition of ``_dispatchable``."""
+    if not _tap_on():
+        return False
+    if not (x.is_cuda and not x.is_meta) or x.dim() != 4:
+        return False
+    if conv.groups != 1 or _pair(conv.dilation) != (1, 1):
+        return False
+    if not (x.dtype == torch.bfloat16 or torch.is_autocast_enabled()):
+        return False
+    if isinstance(conv.padding, str) or conv.padding_mode != "zeros":
+        return False
+    return _tap_ok(x.shape[-2], x.shape[-1], *_pair(conv.kernel_size),
+                   *_pair(conv.stride), *_pair(conv.padding))
+
+
 class NativeConv2d(nn.Conv2d):
     """nn.Conv2d that runs on the gemscore implicit-GEMM MFMA kernels
     when dispatchable (state-dict compatible with nn.Conv2d)."""
 
     def forward(self, x):
-        if _wino_dispatchable(x, self):
+        if _wino_dispatchable(x, self) or _tap_dispatchable(x, self):
             return native_conv2d(x, self.weight, self.bias, self.stride, self.padding)
         if (
             os.environ.get("MPI4DL_WINOGRAD", "0") == "1"

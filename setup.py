@@ -24,6 +24,7 @@ ext = CUDAExtension(
         "mpi4dl_amd/csrc/conv_mfma.hip",
         "mpi4dl_amd/csrc/conv_pw.hip",
         "mpi4dl_amd/csrc/conv_wino.hip",
+        "mpi4dl_amd/csrc/conv_tap.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
