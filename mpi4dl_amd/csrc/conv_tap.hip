@@ -47,12 +47,72 @@
 //   OW % 8 == 0, guarded element stores otherwise.
 // * No atomics, fixed summation order: bit-identical from run to run. No
 //   synchronisation, no host read, no allocation outside torch's allocator.
+//
+// Weight gradient: tap_bwdw_kernel<R, S, XAL, GAL>
+//
+//   gw[k][c][r][s] += sum_{n,oh,ow} go[n][k][oh][ow] * x[n][c][oh-ph+r][ow-pw+s]
+//
+// The forward turned around: the MFMA's k is now 32 pixels of one tile row.
+// For one tap it is the GEMM GO[k][pixels] * X_t[c][pixels]^T, and the R*S
+// taps differ only by a whole-pixel shift of X, so go and the x patch are
+// staged once per pixel tile and a tap is a constant added to the address of
+// the x fragment.
+//
+// * Block (256 threads): 64 output channels x 64 input channels x all taps
+//   of gw, and a contiguous run of `tpb` pixel tiles (over images, tile rows,
+//   tile columns) of TH x TW = 2 x 64 (1x7) or 4 x 32 (7x1, 3x3) pixels: half
+//   of Tile<R,S>, because both operands of a 256-pixel tile do not fit the
+//   160 KB of LDS twice. Accumulators stay in registers over the run; the
+//   block ends with fp32 atomicAdd into gw.
+// * Waves split the block by input channels: wave w owns x channels
+//   c0 + 16w .. +16, all 64 go channels and all taps, 4 x R*S accumulator
+//   fragments (112 / 144 registers). Per 32-pixel k-step a wave reads 4 go
+//   fragments and R*S x fragments for 4 * R*S MFMAs: 0.79 (1x7, 7x1) / 0.72
+//   (3x3) fragment reads per MFMA and no reduction between waves. The two
+//   splits the design note names cost: by output rows 2.1 reads per MFMA; by
+//   pixels (64 x 32 tile, 224 registers a lane) 0.64 but an LDS reduction of
+//   3 x 57 KB, and it spilled in every instantiation (48 - 816 bytes a lane).
+// * Fragments: ds_read_b64_tr_b16 with per-lane row addresses. Lane l of a
+//   16-lane group points at pixel p0 + ((l&15)>>2), channels c + (l&3)*4 and
+//   receives channel c + (l&15) at pixels p0 .. p0+3. Group g takes
+//   p0 = 4g for the first read and 16 + 4g for the second, the same for go
+//   and x, so the MFMA's k slot 8g + e is pixel 4g + e (e < 4) or
+//   16 + 4g + e - 4: any order does, as long as A and B agree.
+// * LDS pixel stride: 160 bytes for both images (64 channels + 32 bytes).
+//   64 banks of 4 bytes; a 16-lane group touches 4 pixels x 32 bytes, and
+//   with the group order above lanes 0 - 31 touch 8 consecutive pixels
+//   p .. p+7 x 32 bytes = 256 bytes, one pass of all banks if the 8 spans are
+//   disjoint. A stride of 32*m bytes puts pixel p on span (p*m) mod 8, so m
+//   must be odd: m = 5 gives 0,5,2,7,4,1,6,3. (128 bytes, m = 4, would put
+//   every second pixel on the same span; with the textbook group order, p0 =
+//   8g, pixels p and p+8 collide for every m.) A tap adds the same offset to
+//   all lanes, so it keeps this. Rows are 128 bytes longer than their pixels:
+//   the 16 lanes of a staging ds_write_b128 pass are 8 channel groups x 2
+//   rows, and whole rows are multiples of 256 bytes apart without it.
+// * Staging: the forward's, as a second copy (struct Operand) used for both
+//   images: the tile moves every step, so offsets and masks are per step, the
+//   stride differs, and the pixel tail of go is one more mask. The forward
+//   keeps its own copy, so its code is unchanged. go and x each choose the
+//   16-byte path on their own (W % 8 resp. OW % 8, base alignment). Double
+//   buffered: loads of tile i+1 before the MFMAs of tile i, commit after
+//   them, one barrier per tile.
+//   x by elements is staged in two passes a step (the second is loaded when
+//   the first is committed, half way through the MFMAs): in one pass the 3x3
+//   kernel spilled.
+// * Only go is zeroed past OH / OW: the x values paired with those pixels are
+//   real image values times zero. A non-finite x there gives NaN in taps whose
+//   true sum does not touch it (conv2d_weight stays finite): inputs are
+//   assumed finite, as in conv_bwd_weight.
+// * Grid: tpb is chosen on the host so that the grid is about 2 blocks per CU
+//   (256 CUs) and at least one per CU where the problem has that many
+//   (output tile, pixel tile) pairs.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 
@@ -63,6 +123,7 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 constexpr int CK = 32;    // channels per chunk (MFMA k)
 constexpr int PSTR = 40;  // shorts per patch pixel: 32 channels + 8 of padding
@@ -390,6 +451,297 @@ __global__ __launch_bounds__(256) void tap_fwd_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Weight gradient (header: "Weight gradient: tap_bwdw_kernel")
+// ---------------------------------------------------------------------------
+
+struct WgGeom {
+  int N, C, H, W, K, OH, OW, ph, pw;
+  int row_blocks, col_blocks;  // pixel tiles of one image
+  int tiles;                   // N * row_blocks * col_blocks
+  int tpb;                     // tiles per block (the run length)
+  int k_tiles, c_tiles;
+};
+
+template <int R, int S>
+struct WgTile {
+  using T = Tile<R, S>;
+  static constexpr int KF = 4, CF = 4;  // 16-channel fragments of go and of x
+  static constexpr int TH = T::TH / 2;  // half the forward's tile: LDS
+  static constexpr int TW = T::TW;
+  static constexpr int PH = TH + R - 1;
+  static constexpr int STR = 80;                     // shorts per pixel
+  static constexpr int GROW = TW * STR + 64;         // shorts per go row
+  static constexpr int XROW = T::PWL * STR + 64;     // shorts per patch row
+  static constexpr int GBUF = TH * GROW;
+  static constexpr int BUF = GBUF + PH * XROW;       // one step: go, then x
+  static constexpr int LDS_SHORTS = 2 * BUF;
+  static_assert(TW % 32 == 0, "a k-step is 32 pixels of one tile row");
+  static_assert(LDS_SHORTS * 2 <= 160 * 1024, "LDS of one CU");
+};
+
+// One operand of a step: ROWS x COLS pixels x NG*8 channels of an NCHW image,
+// staged as [row][column][channel], STR shorts per pixel and ROW per row. The
+// second copy of tap_fwd_kernel's staging (same loads, same v_perm transpose,
+// same masks at commit); what differs is that the tile moves every step, so
+// only `soff` is kept between load and commit and the rest is recomputed.
+// ALIGNED: an item is (8-channel group, row, 8-pixel group of the COLS_L
+// columns in LDS). Otherwise (column of the COLS_N needed ones, 8-channel
+// group, row). The items of a thread are loaded and committed in NP passes, so
+// that only PP of them are in registers at a time.
+template <int ROWS, int COLS_L, int COLS_N, int NG, int STR, int ROW,
+          bool ALIGNED, int NP = 1>
+struct Operand {
+  static constexpr int ITEMS =
+      ALIGNED ? ROWS * (COLS_L / 8) * NG : ROWS * COLS_N * NG;
+  static constexpr int PT = (ITEMS + 255) / 256;  // items per thread
+  static constexpr int PP = (PT + NP - 1) / NP;   // items per pass
+  int soff[PT];  // offset in the channel plane; -1: outside the image
+  i32x4 rawv[ALIGNED ? PP : 1][8];
+  unsigned raws[ALIGNED ? 1 : PP][8];
+
+  static __device__ __forceinline__ void split(int u, int& row, int& col,
+                                               int& cg) {
+    if constexpr (ALIGNED) {
+      cg = u % NG;
+      row = (u / NG) % ROWS;
+      col = (u / NG) / ROWS * 8;
+    } else {
+      col = u % COLS_N;
+      cg = (u / COLS_N) % NG;
+      row = (u / COLS_N) / NG;
+    }
+  }
+
+  // (row0, col0): image coordinates of row 0 and of column index 0
+  __device__ __forceinline__ void locate(int tid, int row0, int col0, int Hi,
+                                         int Wi) {
+#pragma unroll
+    for (int it = 0; it < PT; ++it) {
+      int row, col, cg;
+      split(it * 256 + tid, row, col, cg);
+      const int ih = row0 + row, iw = col0 + col;
+      // ALIGNED: Wi % 8 == 0 and iw % 8 == 0, a group is wholly in or out
+      const bool ok = it * 256 + tid < ITEMS && ih >= 0 && ih < Hi && iw >= 0 &&
+                      iw < Wi;
+      soff[it] = ok ? ih * Wi + iw : -1;
+    }
+  }
+
+  // issue the loads of channels c0 .. c0 + NG*8 (clamped below Cmax: always
+  // inside the image); nothing is read of them before `commit`
+  // (32-bit offsets from a uniform base: an image has fewer than 2^31 elements)
+  template <int PASS = 0>
+  __device__ __forceinline__ void load(const unsigned short* img, int HW,
+                                       int c0, int Cmax, int tid) {
+    constexpr int B = PASS * PP;
+#pragma unroll
+    for (int it = B; it < PT && it < B + PP; ++it) {
+      if (it * 256 + tid >= ITEMS) continue;
+      int row, col, cg;
+      split(it * 256 + tid, row, col, cg);
+      const int off = soff[it] < 0 ? 0 : soff[it];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = c0 + cg * 8 + e;
+        const unsigned short* p =
+            img + (unsigned)((c < Cmax ? c : Cmax - 1) * HW + off);
+        if constexpr (ALIGNED)
+          rawv[it - B][e] = *(const i32x4*)p;
+        else
+          raws[it - B][e] = *p;
+      }
+    }
+  }
+
+  // lc0: LDS column of column index 0. Pads, borders, the pixel tail and the
+  // channel tail become zeros here.
+  template <int PASS = 0>
+  __device__ __forceinline__ void commit(short* buf, int c0, int Cmax, int lc0,
+                                         int tid) {
+    constexpr int B = PASS * PP;
+#pragma unroll
+    for (int it = B; it < PT && it < B + PP; ++it) {
+      if (it * 256 + tid >= ITEMS) continue;
+      int row, col, cg;
+      split(it * 256 + tid, row, col, cg);
+      const unsigned sm = soff[it] < 0 ? 0u : ~0u;
+      unsigned cm[4];  // dword j holds channels 2j (low) and 2j + 1
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = c0 + cg * 8 + 2 * j;
+        cm[j] = sm & ((c < Cmax ? 0xffffu : 0u) | (c + 1 < Cmax ? 0xffff0000u : 0u));
+      }
+      short* dst = buf + row * ROW + (lc0 + col) * STR + cg * 8;
+      if constexpr (ALIGNED) {
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+          // 8x8 transpose of 16-bit values: pixel p of channels 2j and 2j+1
+          const unsigned sel = (p & 1) ? 0x07060302u : 0x05040100u;
+          i32x4 o;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            o[j] = (int)(__builtin_amdgcn_perm(
+                             (unsigned)rawv[it - B][2 * j + 1][p >> 1],
+                             (unsigned)rawv[it - B][2 * j][p >> 1], sel) &
+                         cm[j]);
+          *(i32x4*)(dst + p * STR) = o;
+        }
+      } else {
+        i32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o[j] = (int)((raws[it - B][2 * j] | (raws[it - B][2 * j + 1] << 16)) &
+                       cm[j]);
+        *(i32x4*)dst = o;
+      }
+    }
+  }
+};
+
+// MFMA operand fragment of 16 channels x 32 pixels from a channel-innermost
+// image: p points at (pixel p0 + 4*(lane>>4) + ((lane&15)>>2), channel
+// c0 + (lane&3)*4); the lane receives channel c0 + (lane&15) at pixels
+// p0 + 4*(lane>>4) + {0..3} and, `half` shorts further, at those + 16.
+__device__ __forceinline__ s16x8 read_tr16(const short* p, int half) {
+  auto* q = (__attribute__((address_space(3))) short*)p;
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) s16x4*)q);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) s16x4*)(q + half));
+  s16x8 frag;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    frag[e] = lo[e];
+    frag[e + 4] = hi[e];
+  }
+  return frag;
+}
+
+template <int R, int S, bool XAL, bool GAL>
+__global__ __launch_bounds__(256) void tap_bwdw_kernel(
+    const unsigned short* __restrict__ go, const unsigned short* __restrict__ x,
+    float* __restrict__ gw, WgGeom g) {
+  using T = WgTile<R, S>;
+  using FT = Tile<R, S>;
+  constexpr int RS = R * S, KF = T::KF, CF = T::CF;
+  constexpr int TH = T::TH, TW = T::TW, PADL = FT::PADL;
+  constexpr int STR = T::STR, GROW = T::GROW, XROW = T::XROW;
+  constexpr int KPR = TW / 32;           // k-steps (32 pixels) per tile row
+  constexpr int KS = TH * KPR;           // k-steps per tile
+  static_assert(CF == 4, "one 16-channel fragment of x per wave");
+
+  __shared__ __attribute__((aligned(16))) short lds[T::LDS_SHORTS];
+
+  // block -> (k tile, c tile, run of pixel tiles); XCD-aware bijective swizzle
+  // as in tap_fwd_kernel, so the blocks that share a run share an L2
+  const int nwg = gridDim.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  const int xcd = blockIdx.x & 7, sub = blockIdx.x >> 3;
+  int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + sub;
+  if (bid >= nwg) bid = blockIdx.x;  // never taken: the mapping is bijective
+  const int k0 = (bid % g.k_tiles) * (KF * 16);
+  bid /= g.k_tiles;
+  const int c0 = (bid % g.c_tiles) * (CF * 16);
+  const int run = bid / g.c_tiles;
+  const int t_begin = run * g.tpb;
+  const int t_end = t_begin + g.tpb < g.tiles ? t_begin + g.tpb : g.tiles;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int HW = g.H * g.W, OHW = g.OH * g.OW;
+
+  Operand<TH, TW, TW, KF * 2, STR, GROW, GAL> sg;
+  // x by elements is 5 - 10 items a thread: staged in two passes, the second
+  // loaded when the first is committed, half way through the MFMAs
+  constexpr int NPX = XAL ? 1 : 2;
+  Operand<T::PH, FT::PWL, FT::PWN, CF * 2, STR, XROW, XAL, NPX> sx;
+  const unsigned short* xn = x;  // image of the tile being staged
+  auto stage_load = [&](int tl) {
+    const int cb = tl % g.col_blocks;
+    tl /= g.col_blocks;
+    const int rb = tl % g.row_blocks, n = tl / g.row_blocks;
+    const int oh0 = rb * TH, ow0 = cb * TW;
+    sg.locate(tid, oh0, ow0, g.OH, g.OW);
+    sx.locate(tid, oh0 - g.ph, XAL ? ow0 - PADL : ow0 - g.pw, g.H, g.W);
+    sg.load(go + (int64_t)n * g.K * OHW, OHW, k0, g.K, tid);
+    xn = x + (int64_t)n * g.C * HW;
+    sx.load(xn, HW, c0, g.C, tid);
+  };
+  // two passes: x's first into `buf`, then the loads of its second
+  auto stage_middle = [&](int buf) {
+    if constexpr (NPX == 2) {
+      sx.commit(lds + buf * T::BUF + T::GBUF, c0, g.C, PADL - g.pw, tid);
+      sx.template load<1>(xn, HW, c0, g.C, tid);
+    }
+  };
+  auto stage_commit = [&](int buf) {
+    short* b = lds + buf * T::BUF;
+    sg.commit(b, k0, g.K, 0, tid);
+    sx.template commit<NPX - 1>(b + T::GBUF, c0, g.C, XAL ? 0 : PADL - g.pw,
+                                tid);
+  };
+
+  // fragment addresses of k-step 0 (tile row 0, columns 0 .. 31): this
+  // wave's 16 channels of x, and go's first 16
+  const int px = ((lane >> 4) << 2) + ((lane & 15) >> 2);
+  const int aoff = px * STR + ((lane & 3) << 2);
+  const int boff = (px + PADL - g.pw) * STR + wid * 16 + ((lane & 3) << 2);
+
+  f32x4 acc[KF][RS];
+#pragma unroll
+  for (int kf = 0; kf < KF; ++kf)
+#pragma unroll
+    for (int t = 0; t < RS; ++t) acc[kf][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  stage_load(t_begin);
+  stage_middle(0);
+  stage_commit(0);
+  __syncthreads();
+
+  for (int tl = t_begin; tl < t_end; ++tl) {
+    const int buf = (tl - t_begin) & 1;
+    const bool more = tl + 1 < t_end;
+    if (more) stage_load(tl + 1);
+    const short* gb = lds + buf * T::BUF + aoff;
+    const short* xb = lds + buf * T::BUF + T::GBUF + boff;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      if (ks == KS / 2 && more) stage_middle(buf ^ 1);
+      const int row = ks / KPR, col = (ks % KPR) * 32;
+      s16x8 a[KF];
+#pragma unroll
+      for (int kf = 0; kf < KF; ++kf)
+        a[kf] = read_tr16(gb + row * GROW + col * STR + kf * 16, 16 * STR);
+#pragma unroll
+      for (int t = 0; t < RS; ++t) {
+        const s16x8 b = read_tr16(
+            xb + (row + t / S) * XROW + (col + t % S) * STR, 16 * STR);
+#pragma unroll
+        for (int kf = 0; kf < KF; ++kf)
+          acc[kf][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a[kf], b, acc[kf][t], 0, 0, 0);
+      }
+    }
+    if (more) stage_commit(buf ^ 1);
+    __syncthreads();
+  }
+
+  // D layout of the MFMA: row (lane >> 4)*4 + reg (k), column lane & 15 (c)
+  const int c = c0 + wid * 16 + (lane & 15);
+#pragma unroll
+  for (int kf = 0; kf < KF; ++kf)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int k = k0 + kf * 16 + ((lane >> 4) << 2) + reg;
+      if (k >= g.K || c >= g.C) continue;
+      float* dst = gw + ((int64_t)k * g.C + c) * RS;
+#pragma unroll
+      for (int t = 0; t < RS; ++t) atomicAdd(dst + t, acc[kf][t][reg]);
+    }
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -448,19 +800,20 @@ static TapChoice choose(int K, int W, int R, int S, bool base_aligned) {
 }
 
 static void check_problem(int64_t N, int64_t C, int64_t K, int64_t H, int64_t W,
-                          int64_t R, int64_t S, int64_t ph, int64_t pw) {
+                          int64_t R, int64_t S, int64_t ph, int64_t pw,
+                          const char* who = "tap_fwd") {
   TORCH_CHECK((R == 1 && S == 7) || (R == 7 && S == 1) || (R == 3 && S == 3),
-              "tap_fwd: kernel size must be 1x7, 7x1 or 3x3 (stride 1, "
+              who, ": kernel size must be 1x7, 7x1 or 3x3 (stride 1, "
               "dilation 1, groups 1), got ", R, "x", S);
   TORCH_CHECK(N >= 1 && C >= 1 && K >= 1 && H >= 1 && W >= 1,
-              "tap_fwd: N, C, K, H, W must be positive");
+              who, ": N, C, K, H, W must be positive");
   TORCH_CHECK(ph >= 0 && ph <= R - 1 && pw >= 0 && pw <= S - 1,
-              "tap_fwd: padding must lie in [0, R-1] x [0, S-1], got (", ph,
+              who, ": padding must lie in [0, R-1] x [0, S-1], got (", ph,
               ", ", pw, ") for ", R, "x", S);
   TORCH_CHECK(H + 2 * ph >= R && W + 2 * pw >= S,
-              "tap_fwd: the padded input is smaller than the filter");
+              who, ": the padded input is smaller than the filter");
   TORCH_CHECK(H * W < (1LL << 30) && C < (1LL << 24) && K < (1LL << 24),
-              "tap_fwd: problem too large");
+              who, ": problem too large");
 }
 
 static TapGeom make_geom(int64_t N, int64_t C, int64_t K, int64_t H, int64_t W,
@@ -535,6 +888,126 @@ torch::Tensor tap_fwd(torch::Tensor x, torch::Tensor w,
   return out;
 }
 
+// ---- weight gradient --------------------------------------------------------
+
+using WgKern = void (*)(const unsigned short*, const unsigned short*, float*,
+                        WgGeom);
+
+// The launch of a weight-gradient problem: the only place that decides the
+// instantiation, the run length and the grid.
+struct WgChoice {
+  WgKern kern;
+  WgGeom g;
+  int64_t blocks;
+  std::string label;
+};
+
+template <int R, int S>
+static WgChoice choose_bwdw_rs(WgGeom g, bool xal, bool gal,
+                               int64_t tiles_per_block) {
+  using T = WgTile<R, S>;
+  constexpr int CUS = 256;
+  g.row_blocks = (g.OH + T::TH - 1) / T::TH;
+  g.col_blocks = (g.OW + T::TW - 1) / T::TW;
+  const int64_t tiles = (int64_t)g.N * g.row_blocks * g.col_blocks;
+  TORCH_CHECK(tiles < (1LL << 31), "tap_bwd_weight: problem too large");
+  g.tiles = (int)tiles;
+  g.k_tiles = (g.K + T::KF * 16 - 1) / (T::KF * 16);
+  g.c_tiles = (g.C + T::CF * 16 - 1) / (T::CF * 16);
+  // about two blocks per CU; at least one per CU where there are that many
+  // (output tile, pixel tile) pairs
+  const int64_t ot = (int64_t)g.k_tiles * g.c_tiles;
+  int64_t tpb = tiles_per_block;
+  if (tpb <= 0) {
+    const int64_t runs = std::max<int64_t>(1, 2 * CUS / ot);
+    // where tiles >= runs, ceil(tiles / tpb) > runs / 2, so the grid has at
+    // least ot * (runs + 1) / 2 > CUS blocks; with fewer tiles tpb is 1 and
+    // the grid is every (output tile, pixel tile) pair
+    tpb = (tiles + runs - 1) / runs;
+  }
+  tpb = std::min<int64_t>(tpb, tiles);
+  g.tpb = (int)tpb;
+  const int64_t blocks = ot * ((tiles + tpb - 1) / tpb);
+  const WgKern k = xal ? (gal ? tap_bwdw_kernel<R, S, true, true>
+                              : tap_bwdw_kernel<R, S, true, false>)
+                       : (gal ? tap_bwdw_kernel<R, S, false, true>
+                              : tap_bwdw_kernel<R, S, false, false>);
+  return {k, g, blocks,
+          "tap_bwdw<" + std::to_string(R) + "x" + std::to_string(S) + "," +
+              std::to_string(T::KF * 16) + "x" + std::to_string(T::CF * 16) +
+              ",tpb" + std::to_string(tpb) + ">"};
+}
+
+static WgChoice choose_bwdw(int64_t N, int64_t C, int64_t K, int64_t H,
+                            int64_t W, int64_t R, int64_t S, int64_t ph,
+                            int64_t pw, bool x_aligned, bool go_aligned,
+                            int64_t tiles_per_block) {
+  check_problem(N, C, K, H, W, R, S, ph, pw, "tap_bwd_weight");
+  WgGeom g;
+  g.N = (int)N; g.C = (int)C; g.K = (int)K; g.H = (int)H; g.W = (int)W;
+  g.ph = (int)ph; g.pw = (int)pw;
+  g.OH = g.H + 2 * g.ph - (int)R + 1;
+  g.OW = g.W + 2 * g.pw - (int)S + 1;
+  // the kernel addresses one image of x and of go with 32-bit offsets
+  TORCH_CHECK(C * H * W < (1LL << 31) && K * g.OH * g.OW < (1LL << 31),
+              "tap_bwd_weight: problem too large");
+  const bool xal = x_aligned && g.W % 8 == 0;
+  const bool gal = go_aligned && g.OW % 8 == 0;
+  if (R == 1) return choose_bwdw_rs<1, 7>(g, xal, gal, tiles_per_block);
+  if (R == 7) return choose_bwdw_rs<7, 1>(g, xal, gal, tiles_per_block);
+  return choose_bwdw_rs<3, 3>(g, xal, gal, tiles_per_block);
+}
+
+std::string tap_bwdw_kernel_name(int64_t N, int64_t C, int64_t K, int64_t H,
+                                 int64_t W, int64_t R, int64_t S, int64_t ph,
+                                 int64_t pw) {
+  return choose_bwdw(N, C, K, H, W, R, S, ph, pw, true, true, 0).label;
+}
+
+// gw[k][c][r][s] += sum over n, oh, ow of go[n][k][oh][ow] *
+// x[n][c][oh-ph+r][ow-pw+s]. With `out` (fp32, contiguous, K*C*R*S elements,
+// go's device) the kernel's atomicAdd accumulates into it; without, into a
+// fresh zeroed tensor: conv_bwd_weight's contract.
+torch::Tensor tap_bwd_weight(torch::Tensor go, torch::Tensor x, int64_t R,
+                             int64_t S, int64_t ph, int64_t pw,
+                             c10::optional<torch::Tensor> out,
+                             int64_t tiles_per_block) {
+  TORCH_CHECK(go.is_cuda() && x.is_cuda() && go.get_device() == x.get_device(),
+              "tap_bwd_weight: go and x must be on one GPU");
+  TORCH_CHECK(go.dim() == 4 && x.dim() == 4 && go.is_contiguous() &&
+                  x.is_contiguous(),
+              "tap_bwd_weight: go and x must be contiguous 4-d tensors");
+  TORCH_CHECK(go.scalar_type() == torch::kBFloat16 &&
+                  x.scalar_type() == torch::kBFloat16,
+              "tap_bwd_weight: bf16 only");
+  const WgChoice ch = choose_bwdw(
+      x.size(0), x.size(1), go.size(1), x.size(2), x.size(3), R, S, ph, pw,
+      ((uintptr_t)x.data_ptr() & 15) == 0, ((uintptr_t)go.data_ptr() & 15) == 0,
+      tiles_per_block);
+  const WgGeom& g = ch.g;
+  TORCH_CHECK(go.size(0) == g.N && go.size(2) == g.OH && go.size(3) == g.OW,
+              "tap_bwd_weight: go is not the gradient of this convolution");
+  const int64_t numel = (int64_t)g.K * g.C * R * S;
+  torch::Tensor gw;
+  if (out.has_value()) {
+    gw = *out;
+    TORCH_CHECK(gw.is_cuda() && gw.get_device() == go.get_device() &&
+                    gw.scalar_type() == torch::kFloat && gw.is_contiguous() &&
+                    gw.numel() == numel,
+                "tap_bwd_weight: out must be a contiguous fp32 tensor of "
+                "K*C*R*S elements on go's device");
+  } else {
+    gw = torch::zeros({numel}, x.options().dtype(torch::kFloat));
+  }
+  TORCH_CHECK(ch.blocks < (1LL << 31), "tap_bwd_weight: grid too large");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(ch.kern, dim3((uint32_t)ch.blocks), dim3(256), 0,
+                     stream.stream(), (const unsigned short*)go.data_ptr(),
+                     (const unsigned short*)x.data_ptr(), gw.data_ptr<float>(),
+                     g);
+  return gw.view({(int64_t)g.K, (int64_t)g.C, R, S});
+}
+
 }  // namespace conv_tap
 
 void register_conv_tap(pybind11::module_& m) {
@@ -547,4 +1020,15 @@ void register_conv_tap(pybind11::module_& m) {
   m.def("tap_kernel_name", &conv_tap::tap_kernel_name,
         "label of the kernel tap_fwd launches for (C, K, H, W, R, S, ph, pw); "
         "no tensor, no HIP call");
+  m.def("tap_bwd_weight", &conv_tap::tap_bwd_weight, pybind11::arg("go"),
+        pybind11::arg("x"), pybind11::arg("R"), pybind11::arg("S"),
+        pybind11::arg("ph"), pybind11::arg("pw"),
+        pybind11::arg("out") = pybind11::none(),
+        pybind11::arg("tiles_per_block") = 0,
+        "tap-shift MFMA weight gradient of a stride-1 1x7 / 7x1 / 3x3 conv "
+        "(bf16 NCHW in, fp32 [K, C, R, S] out); adds into `out` when given; "
+        "tiles_per_block > 0 overrides the chooser's run length");
+  m.def("tap_bwdw_kernel_name", &conv_tap::tap_bwdw_kernel_name,
+        "label of the kernel tap_bwd_weight launches for (N, C, K, H, W, R, S, "
+        "ph, pw); no tensor, no HIP call");
 }

@@ -31,7 +31,14 @@ Kernel families (csrc/):
   (PERF_NOTES, "Tap-shift conv"): both legs beat MIOpen at the 512²,
   256² and 128² planes and lose at 64²; the switch as a whole is 0.89x
   end to end because of the weight-grad leg. The default dispatch does
-  not use it.
+  not use it. The third leg of the triple is tap_bwdw_kernel in the same
+  file: go and x staged once per pixel tile, channel-innermost, MFMA k
+  over pixels through transposing LDS reads, every tap an address offset
+  into the x patch, fp32 atomicAdd into gw (so it feeds the gradient
+  sink). Opt-in on top of the first switch: MPI4DL_TAPCONV_WGRAD=1 sends
+  the weight-grad of every problem that MPI4DL_TAPCONV=1 routes to
+  ge.tap_bwd_weight; alone it changes nothing (PERF_NOTES, "Tap-shift
+  weight gradient").
 
 Per-shape, per-LEG policy (all crossovers measured on MI355X —
 profiles/PERF_NOTES.md): stride-2 1x1s, K<=64 1x1s, stems, wide
@@ -44,11 +51,12 @@ F.conv2d/MIOpen. MPI4DL_NATIVE_CONV=0 disables all native paths,
 
 The per-leg policy is written once, in ``conv_plan``: a pure function
 of the problem's integers and the MPI4DL_PW_BLASLT,
-MPI4DL_WINOGRAD=fused and MPI4DL_TAPCONV=1 switches. ``ConvFn``
-executes the plan and decides nothing itself; which kernel a native
-route then launches is the extension's choice (``conv_fwd_kernel_name``,
-``pw_kernel_name``, ``pw_bwdw_kernel_name``, ``wino_kernel_name``,
-``tap_kernel_name`` answer it for a plan's problems).
+MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1 and MPI4DL_TAPCONV_WGRAD=1
+switches. ``ConvFn`` executes the plan and decides nothing itself; which
+kernel a native route then launches is the extension's choice
+(``conv_fwd_kernel_name``, ``pw_kernel_name``, ``pw_bwdw_kernel_name``,
+``wino_kernel_name``, ``tap_kernel_name``, ``tap_bwdw_kernel_name``
+answer it for a plan's problems).
 """
 
 from __future__ import annotations
@@ -105,6 +113,10 @@ def _tap_on():
     return os.environ.get("MPI4DL_TAPCONV", "0") == "1"
 
 
+def _tap_wgrad_on():
+    return os.environ.get("MPI4DL_TAPCONV_WGRAD", "0") == "1"
+
+
 def _tap_ok(H, W, R, S, sh, sw, ph, pw):
     """What conv_tap.hip serves: 1x7, 7x1 or 3x3, stride 1, pads in
     [0, R-1] x [0, S-1], at least one output pixel (dilation 1 and groups
@@ -139,6 +151,9 @@ class Leg(NamedTuple):
                              gradient); problem = tap_kernel_name's
                              (C, K, H, W, R, S, ph, pw), C and K as for
                              wino_fwd
+      tap_bwd_weight         ge.tap_bwd_weight; problem =
+                             tap_bwdw_kernel_name's (N, C, K, H, W, R, S,
+                             ph, pw), the forward convolution's
     """
 
     route: str
@@ -152,12 +167,13 @@ class ConvPlan(NamedTuple):
 
 
 def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
-              winograd=None, tap=None):
+              winograd=None, tap=None, tap_wgrad=None):
     """The route of each leg of the convolution x[N,C,H,W] * w[K,C,R,S]
     and the problem that route hands to its binding. ``blaslt`` defaults
     to the MPI4DL_PW_BLASLT switch, ``winograd`` to
-    MPI4DL_WINOGRAD == "fused" and ``tap`` to MPI4DL_TAPCONV == "1";
-    nothing else is read."""
+    MPI4DL_WINOGRAD == "fused", ``tap`` to MPI4DL_TAPCONV == "1" and
+    ``tap_wgrad`` (looked at only where ``tap`` routes the problem) to
+    MPI4DL_TAPCONV_WGRAD == "1"; nothing else is read."""
     if blaslt is None:
         blaslt = _blaslt_on()
     if winograd is None:
@@ -209,11 +225,14 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
     if tap and _tap_ok(H, W, R, S, sh, sw, ph, pw):
         # opt-in tap-shift kernel: forward, and the data-grad as the same
         # kernel on go with the complementary pads; the weight-grad keeps
-        # its kernel
+        # its kernel unless the second switch sends it to tap_bwd_weight
+        if tap_wgrad is None:
+            tap_wgrad = _tap_wgrad_on()
         return ConvPlan(
             Leg("tap_fwd", (C, K, H, W, R, S, ph, pw)),
             Leg("tap_fwd", (K, C, OH, OW, R, S, R - 1 - ph, S - 1 - pw)),
-            Leg("conv_bwd_weight", fwd),
+            (Leg("tap_bwd_weight", (N, C, K, H, W, R, S, ph, pw))
+             if tap_wgrad else Leg("conv_bwd_weight", fwd)),
         )
     if (sh, sw) == (1, 1):
         # stride-1 data-grad = the forward kernel on C<->K transposed,
@@ -238,7 +257,8 @@ class ConvFn(torch.autograd.Function):
     between a forward and its backward is ignored.
 
     Weight gradient: the routes that run our own kernels (pw_bwdw,
-    pw_bwdw_sub, conv_bwd_weight) add it straight into ``w.grad`` when
+    pw_bwdw_sub, conv_bwd_weight, tap_bwd_weight) add it straight into
+    ``w.grad`` when
     ``grad_sink(w)`` allows, and backward then returns None for ``w``;
     otherwise, and on the bmm route, it is returned for autograd to
     accumulate."""
@@ -296,6 +316,8 @@ class ConvFn(torch.autograd.Function):
             out = () if sink is None else (sink,)
             if gw_route == "conv_bwd_weight":
                 gw = ge.conv_bwd_weight(go, xb, R, S, sh, sw, ph, pw, *out)
+            elif gw_route == "tap_bwd_weight":
+                gw = ge.tap_bwd_weight(go, xb, R, S, ph, pw, *out)
             else:
                 xs = (xb if gw_route == "pw_bwdw"
                       else xb[:, :, ::sh, ::sw].contiguous())
