@@ -154,22 +154,24 @@ def tap_ab(args):
 
 def tap_bwdw_ab(args):
     """The shapes of --tap, weight-gradient leg only: the tap-shift kernel
-    (ge.tap_bwd_weight), our general kernel (ge.conv_bwd_weight) and MIOpen
+    (ge.tap_bwd_weight), its rolling-window variant (ge.tap_bwd_weight_ring),
+    our general kernel (ge.conv_bwd_weight) and MIOpen
     (torch.nn.grad.conv2d_weight on bf16 tensors). Same protocol as --tap:
     all variants warmed up, five alternating rounds, the median round.
     Ratios are MIOpen's time over the variant's."""
     from mpi4dl_amd.ops import backend
 
     ge = backend.ext()
-    names = ("tap", "bwdw", "miopen")
+    names = ("ring", "tap", "bwdw", "miopen")
     print(f"{'shape':<34}" + "".join(f"{n:>11}" for n in names)
-          + "   tap/bwdw vs miopen  tap vs bwdw  winner")
+          + "   ring/tap/bwdw vs miopen  tap vs bwdw  ring vs tap  winner")
     for C, hw, R, S in TAP_SHAPES:
         ph, pw = R // 2, S // 2
         N = args.batch
         x = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
         go = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
         fns = {
+            "ring": lambda: ge.tap_bwd_weight_ring(go, x, R, S, ph, pw),
             "tap": lambda: ge.tap_bwd_weight(go, x, R, S, ph, pw),
             "bwdw": lambda: ge.conv_bwd_weight(go, x, R, S, 1, 1, ph, pw),
             "miopen": lambda: torch.nn.grad.conv2d_weight(
@@ -184,15 +186,18 @@ def tap_bwdw_ab(args):
                     timeit(fns[n], max(args.iters // 5, 2), warmup=0))
         t = {n: sorted(v)[len(v) // 2] for n, v in rounds.items()}
         ref = fns["miopen"]().float()
-        rel = ((fns["tap"]() - ref).abs().max().item()
-               / max(ref.abs().max().item(), 1e-3))
+        rel = {n: ((fns[n]() - ref).abs().max().item()
+                   / max(ref.abs().max().item(), 1e-3)) for n in names[:2]}
         tag = f"C{C}->K{C} {hw}x{hw} k{R}x{S} N{N}"
         print(f"{tag:<34}"
               + "".join(f"{t[n]:9.3f}ms" for n in names) + "   "
-              + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:2])
-              + f"  {t['bwdw'] / t['tap']:5.2f}x  {min(t, key=t.get):<7}"
-              f"[{ge.tap_bwdw_kernel_name(N, C, C, hw, hw, R, S, ph, pw)}]"
-              f"  tap relerr {rel:.3g}", flush=True)
+              + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:3])
+              + f"  {t['bwdw'] / t['tap']:5.2f}x  {t['tap'] / t['ring']:5.2f}x"
+              f"  {min(t, key=t.get):<7}"
+              f"[{ge.tap_bwdw_ring_kernel_name(N, C, C, hw, hw, R, S, ph, pw)}, "
+              f"{ge.tap_bwdw_kernel_name(N, C, C, hw, hw, R, S, ph, pw)}]"
+              f"  ring relerr {rel['ring']:.3g} tap relerr {rel['tap']:.3g}",
+              flush=True)
 
 
 def model_pw_shapes(num_layers=18, num_filters=416, image=2048, mb=2):
@@ -373,8 +378,9 @@ def main():
                          "MIOpen on the stride-1 1x7, 7x1 and 3x3 shapes, "
                          "forward and data-grad")
     ap.add_argument("--tap-bwdw", action="store_true",
-                    help="A/B the tap-shift weight-gradient kernel and "
-                         "conv_bwd_weight vs MIOpen on the shapes of --tap")
+                    help="A/B the tap-shift weight-gradient kernels (rolling "
+                         "window and first) and conv_bwd_weight vs MIOpen on "
+                         "the shapes of --tap")
     ap.add_argument("--pw", action="store_true",
                     help="A/B the conv_pw 1x1 kernel vs MIOpen on the "
                          "flagship model's 1x1 shapes")

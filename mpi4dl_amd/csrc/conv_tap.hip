@@ -106,6 +106,51 @@
 // * Grid: tpb is chosen on the host so that the grid is about 2 blocks per CU
 //   (256 CUs) and at least one per CU where the problem has that many
 //   (output tile, pixel tile) pairs.
+//
+// Weight gradient, rolling window: tap_bwdw_ring_kernel<R, S, NARROW, XAL, GAL>
+//
+// The same GEMM, fragments, k-slot order and staging (struct Operand,
+// unchanged) on a block small enough that two are resident on a CU, and that
+// stages every x row once.
+//
+// * Block (256 threads): 32 output channels x 64 input channels (NARROW: 32 x
+//   32) x all taps, and one strip: a band of TW = 64 (1x7) or 32 (7x1, 3x3)
+//   output columns of one image over `rows` consecutive output rows, walked
+//   downwards in steps of TH = 2 rows (128 / 64 pixels between barriers).
+// * Waves: by input channels, 16 each, KF = 2 go fragments: 2 x R*S
+//   accumulator fragments (56 / 72 registers), 2 + R*S fragment reads for
+//   2 * R*S MFMAs per k-step. NARROW: 2 x 2 over go and x fragments, R*S
+//   accumulators (28 / 36), 1 + R*S reads for R*S MFMAs.
+// * Ring. Rows are staged in units of TH. Step i reads go unit i and x units
+//   i .. i + D, D = ceil((R - 1) / TH) = 0 / 3 / 1, and while it computes,
+//   unit i + 1 + D is committed: SLOTS = D + 2 units of x (4 / 10 / 6 rows)
+//   and 2 of go. Unit u lies in slot u mod SLOTS, so a unit never wraps and
+//   staging writes whole units; patch row q of step i is ring row
+//   (i*TH mod RROWS) + q, minus RROWS where that is past the end: one
+//   compare-and-subtract on a uniform value per patch row and step, then the
+//   tap is the old constant offset. For 1x7, D = 0: plain double buffering.
+// * Prefetch. x on the 16-byte path has two register sets: the loads of step
+//   i + 2 are issued at the top of step i and committed at the end of step
+//   i + 1, into the slot last read in step i - 1. go, and x by elements, are
+//   loaded at the top of step i and committed at its end (one step ahead, one
+//   set): with two sets of each the wide instantiations spilled. One barrier
+//   per step.
+// * LDS: go 96 bytes a pixel (32 channels + 32 bytes: 32*3, odd, so the same
+//   span argument as above holds: 0,3,6,1,4,7,2,5), x 160 (NARROW: 96); rows
+//   128 bytes longer. go 2 units + x SLOTS units:
+//     1x7  4 * 6272 + 4 * 12928 = 76800 B   (NARROW 56320)
+//     7x1  4 * 3200 + 10 * 5248 = 65280 B   (NARROW 44800)
+//     3x3  4 * 3200 + 6 * 7808  = 59648 B   (NARROW 41216)
+//   all at most 80 KB, and __launch_bounds__(256, 2) holds the registers to
+//   256 a lane: two blocks per CU.
+// * Grid: k and c tiles of a strip innermost (one XCD's L2), then strips,
+//   bands, images. The strip length is chosen on the host so that the grid is
+//   at least 4 x 256 blocks where the problem has that many steps.
+// * NARROW is chosen where C rounded up to 32 is less than C rounded up to 64
+//   (C = 20: 32 against 64; C = 52 is 64 under both and stays wide), and
+//   wherever x is staged by elements (W % 8 != 0 or an unaligned base): the
+//   three of the wide tile's six such instantiations spilled 96 - 352 bytes a
+//   lane, and none of the six is built.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -742,6 +787,190 @@ __global__ __launch_bounds__(256) void tap_bwdw_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Weight gradient, rolling window (header: "tap_bwdw_ring_kernel")
+// ---------------------------------------------------------------------------
+
+struct RingGeom {
+  int N, C, H, W, K, OH, OW, ph, pw;
+  int col_bands;        // bands of TW output columns of one image
+  int strips_per_band;  // strips of `rows` output rows of one band
+  int rows;             // output rows of a strip: a multiple of TH
+  int k_tiles, c_tiles;
+};
+
+template <int R, int S, bool NARROW>
+struct RingTile {
+  using T = Tile<R, S>;
+  static constexpr int KB = 32, CB = NARROW ? 32 : 64;  // channels of go, of x
+  static constexpr int TH = 2, TW = T::TW;              // pixels of a step
+  // a unit is TH rows; step i reads x units i .. i + D and go unit i
+  static constexpr int D = (R - 1 + TH - 1) / TH;
+  static constexpr int SLOTS = D + 2;                // x units in the ring
+  static constexpr int RROWS = SLOTS * TH;           // x rows in the ring
+  static constexpr int GSTR = 48;                    // shorts per go pixel
+  static constexpr int XSTR = NARROW ? 48 : 80;      // shorts per x pixel
+  static constexpr int GROW = TW * GSTR + 64;        // shorts per go row
+  static constexpr int XROW = T::PWL * XSTR + 64;    // shorts per x row
+  static constexpr int GUNIT = TH * GROW, XUNIT = TH * XROW;
+  static constexpr int GRING = 2 * GUNIT;            // go: two units
+  static constexpr int LDS_SHORTS = GRING + SLOTS * XUNIT;
+  static_assert(TW % 32 == 0, "a k-step is 32 pixels of one row");
+  static_assert(D * TH >= R - 1, "the units of a step cover its patch");
+  static_assert(LDS_SHORTS * 2 <= 80 * 1024, "two blocks per CU");
+};
+
+template <int R, int S, bool NARROW, bool XAL, bool GAL>
+__global__ __launch_bounds__(256, 2) void tap_bwdw_ring_kernel(
+    const unsigned short* __restrict__ go, const unsigned short* __restrict__ x,
+    float* __restrict__ gw, RingGeom g) {
+  using T = RingTile<R, S, NARROW>;
+  using FT = Tile<R, S>;
+  constexpr int RS = R * S, KB = T::KB, CB = T::CB;
+  constexpr int TH = T::TH, TW = T::TW, PADL = FT::PADL, D = T::D;
+  constexpr int GSTR = T::GSTR, XSTR = T::XSTR, GROW = T::GROW, XROW = T::XROW;
+  constexpr int KFW = NARROW ? 1 : 2;    // go fragments of a wave
+  constexpr int KPR = TW / 32;           // k-steps (32 pixels) per row
+  constexpr int KS = TH * KPR;           // k-steps per step
+
+  __shared__ __attribute__((aligned(16))) short lds[T::LDS_SHORTS];
+  short* gring = lds;
+  short* xring = lds + T::GRING;
+
+  // block -> (k tile, c tile, strip, band, image); XCD-aware bijective swizzle
+  // as in tap_bwdw_kernel: the k and c tiles of a strip are consecutive, so
+  // they share an L2
+  const int nwg = gridDim.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  const int xcd = blockIdx.x & 7, sub = blockIdx.x >> 3;
+  int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + sub;
+  if (bid >= nwg) bid = blockIdx.x;  // never taken: the mapping is bijective
+  const int k0 = (bid % g.k_tiles) * KB;
+  bid /= g.k_tiles;
+  const int c0 = (bid % g.c_tiles) * CB;
+  bid /= g.c_tiles;
+  const int oh_b = (bid % g.strips_per_band) * g.rows;
+  bid /= g.strips_per_band;
+  const int ow0 = (bid % g.col_bands) * TW;
+  const int n = bid / g.col_bands;
+  const int oh_e = oh_b + g.rows < g.OH ? oh_b + g.rows : g.OH;
+  const int steps = (oh_e - oh_b + TH - 1) / TH;  // >= 1: oh_b < OH
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int HW = g.H * g.W, OHW = g.OH * g.OW;
+  const unsigned short* gon = go + (int64_t)n * g.K * OHW;
+  const unsigned short* xn = x + (int64_t)n * g.C * HW;
+
+  // x on the 16-byte path has two register sets: the loads of step i + 2 are
+  // issued while those of step i + 1 are still uncommitted. go, and x by
+  // elements, are loaded one step ahead into one set: with two the wide
+  // instantiations spilled.
+  using OpG = Operand<TH, TW, TW, KB / 8, GSTR, GROW, GAL>;
+  using OpX = Operand<TH, FT::PWL, FT::PWN, CB / 8, XSTR, XROW, XAL>;
+  OpG sg;
+  OpX sx0, sx1;
+  const int xcol0 = XAL ? ow0 - PADL : ow0 - g.pw;
+  const int xlc0 = XAL ? 0 : PADL - g.pw;
+  // x unit u of the strip: input rows oh_b - ph + u*TH .. + TH
+  auto load_x = [&](OpX& sx, int u) {
+    sx.locate(tid, oh_b - g.ph + u * TH, xcol0, g.H, g.W);
+    sx.load(xn, HW, c0, g.C, tid);
+  };
+  // what step d adds to the rings: go unit d (zero below the strip) and x
+  // unit d + D
+  auto load_g = [&](int d) {
+    sg.locate(tid, oh_b + d * TH, ow0, oh_e, g.OW);
+    sg.load(gon, OHW, k0, g.K, tid);
+  };
+  auto commit = [&](OpX& sx, int d, int xslot) {
+    sg.commit(gring + (d & 1) * T::GUNIT, k0, g.K, 0, tid);
+    sx.commit(xring + xslot * T::XUNIT, c0, g.C, xlc0, tid);
+  };
+
+  // fragment addresses of k-step 0 of ring row 0: this wave's channels
+  const int kw = NARROW ? (wid & 1) : 0, cw = NARROW ? (wid >> 1) : wid;
+  const int px = ((lane >> 4) << 2) + ((lane & 15) >> 2);
+  const int aoff = px * GSTR + kw * 16 + ((lane & 3) << 2);
+  const int boff = (px + PADL - g.pw) * XSTR + cw * 16 + ((lane & 3) << 2);
+
+  f32x4 acc[KFW][RS];
+#pragma unroll
+  for (int kf = 0; kf < KFW; ++kf)
+#pragma unroll
+    for (int t = 0; t < RS; ++t) acc[kf][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // fill: the D units above step 0's own, then step 0; step 1 in flight
+#pragma unroll
+  for (int u = 0; u < D; ++u) {
+    load_x(sx0, u);
+    sx0.commit(xring + u * T::XUNIT, c0, g.C, xlc0, tid);
+  }
+  load_g(0);
+  load_x(sx0, D);
+  commit(sx0, 0, D);
+  if (XAL && steps > 1) load_x(sx1, 1 + D);
+  __syncthreads();
+
+  int cslot = D + 1;  // ring slot of x unit i + 1 + D
+  int base = 0;       // ring row of the step's first patch row
+  // step i: x loads of i + 2 into set A (by elements: of i + 1 into set B), go
+  // loads of i + 1, MFMAs of i, commit of i + 1 from set B (its slots were
+  // last read in step i - 1), one barrier
+  auto step = [&](int i, OpX& sxA, OpX& sxB) {
+    if (XAL && i + 2 < steps) load_x(sxA, i + 2 + D);
+    if (!XAL && i + 1 < steps) load_x(sxB, i + 1 + D);
+    if (i + 1 < steps) load_g(i + 1);
+    const short* gb = gring + (i & 1) * T::GUNIT + aoff;
+    const short* xb = xring + boff;
+    int xrow[TH + R - 1];  // patch row q of this step in the ring
+#pragma unroll
+    for (int q = 0; q < TH + R - 1; ++q) {
+      const int r = base + q;
+      xrow[q] = (r >= T::RROWS ? r - T::RROWS : r) * XROW;
+    }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int row = ks / KPR, col = (ks % KPR) * 32;
+      s16x8 a[KFW];
+#pragma unroll
+      for (int kf = 0; kf < KFW; ++kf)
+        a[kf] = read_tr16(gb + row * GROW + col * GSTR + kf * 16, 16 * GSTR);
+#pragma unroll
+      for (int t = 0; t < RS; ++t) {
+        const s16x8 b = read_tr16(
+            xb + xrow[row + t / S] + (col + t % S) * XSTR, 16 * XSTR);
+#pragma unroll
+        for (int kf = 0; kf < KFW; ++kf)
+          acc[kf][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a[kf], b, acc[kf][t], 0, 0, 0);
+      }
+    }
+    if (i + 1 < steps) commit(sxB, i + 1, cslot);
+    cslot = cslot + 1 == T::SLOTS ? 0 : cslot + 1;
+    base = base + TH == T::RROWS ? 0 : base + TH;
+    __syncthreads();
+  };
+  for (int i = 0; i < steps; i += 2) {
+    step(i, sx0, sx1);
+    if (i + 1 < steps) step(i + 1, sx1, sx0);
+  }
+
+  // D layout of the MFMA: row (lane >> 4)*4 + reg (k), column lane & 15 (c)
+  const int c = c0 + cw * 16 + (lane & 15);
+#pragma unroll
+  for (int kf = 0; kf < KFW; ++kf)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int k = k0 + (kw + kf) * 16 + ((lane >> 4) << 2) + reg;
+      if (k >= g.K || c >= g.C) continue;
+      float* dst = gw + ((int64_t)k * g.C + c) * RS;
+#pragma unroll
+      for (int t = 0; t < RS; ++t) atomicAdd(dst + t, acc[kf][t][reg]);
+    }
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -1008,6 +1237,134 @@ torch::Tensor tap_bwd_weight(torch::Tensor go, torch::Tensor x, int64_t R,
   return gw.view({(int64_t)g.K, (int64_t)g.C, R, S});
 }
 
+// ---- weight gradient, rolling window ----------------------------------------
+
+using RingKern = void (*)(const unsigned short*, const unsigned short*, float*,
+                          RingGeom);
+
+// The launch of a rolling-window problem: the only place that decides the
+// instantiation, the strip length and the grid.
+struct RingChoice {
+  RingKern kern;
+  RingGeom g;
+  int64_t blocks;
+  std::string label;
+};
+
+template <int R, int S, bool NARROW>
+static RingChoice choose_ring_rs(RingGeom g, bool xal, bool gal,
+                                 int64_t strip_rows) {
+  using T = RingTile<R, S, NARROW>;
+  constexpr int64_t GRID = 4 * 256;  // two resident blocks per CU, two rounds
+  g.col_bands = (g.OW + T::TW - 1) / T::TW;
+  g.k_tiles = (g.K + T::KB - 1) / T::KB;
+  g.c_tiles = (g.C + T::CB - 1) / T::CB;
+  const int64_t ot = (int64_t)g.k_tiles * g.c_tiles;
+  const int64_t bands = (int64_t)g.N * g.col_bands;
+  const int64_t row_steps = (g.OH + T::TH - 1) / T::TH;  // steps of one band
+  // `need` strips a band make ot * bands * need >= GRID blocks. With
+  // spb = floor(row_steps / need) steps a strip, a band has
+  // ceil(row_steps / spb) >= need strips wherever row_steps >= need; with
+  // fewer steps spb is 1 and the grid is every (output tile, step) pair.
+  int64_t spb = (strip_rows + T::TH - 1) / T::TH;
+  if (strip_rows <= 0) {
+    const int64_t need = (GRID + ot * bands - 1) / (ot * bands);
+    spb = row_steps / need;
+  }
+  spb = std::min(std::max<int64_t>(spb, 1), row_steps);
+  g.rows = (int)(spb * T::TH);
+  g.strips_per_band = (int)((row_steps + spb - 1) / spb);
+  const int64_t blocks = ot * bands * g.strips_per_band;
+  RingKern k = gal ? tap_bwdw_ring_kernel<R, S, NARROW, true, true>
+                   : tap_bwdw_ring_kernel<R, S, NARROW, true, false>;
+  if constexpr (NARROW) {  // the wide tile is built for the 16-byte x path only
+    if (!xal)
+      k = gal ? tap_bwdw_ring_kernel<R, S, true, false, true>
+              : tap_bwdw_ring_kernel<R, S, true, false, false>;
+  } else {
+    TORCH_INTERNAL_ASSERT(xal);  // choose_ring sends x by elements to NARROW
+  }
+  return {k, g, blocks,
+          "tap_bwdw_ring<" + std::to_string(R) + "x" + std::to_string(S) + "," +
+              std::to_string(T::KB) + "x" + std::to_string(T::CB) + ",rows" +
+              std::to_string(g.rows) + ">"};
+}
+
+static RingChoice choose_ring(int64_t N, int64_t C, int64_t K, int64_t H,
+                              int64_t W, int64_t R, int64_t S, int64_t ph,
+                              int64_t pw, bool x_aligned, bool go_aligned,
+                              int64_t strip_rows) {
+  check_problem(N, C, K, H, W, R, S, ph, pw, "tap_bwd_weight_ring");
+  RingGeom g;
+  g.N = (int)N; g.C = (int)C; g.K = (int)K; g.H = (int)H; g.W = (int)W;
+  g.ph = (int)ph; g.pw = (int)pw;
+  g.OH = g.H + 2 * g.ph - (int)R + 1;
+  g.OW = g.W + 2 * g.pw - (int)S + 1;
+  // the kernel addresses one image of x and of go with 32-bit offsets
+  TORCH_CHECK(C * H * W < (1LL << 31) && K * g.OH * g.OW < (1LL << 31),
+              "tap_bwd_weight_ring: problem too large");
+  const bool xal = x_aligned && g.W % 8 == 0;
+  const bool gal = go_aligned && g.OW % 8 == 0;
+  // the 32-channel c tile where it pads fewer channels than the 64 tile, and
+  // wherever x is staged by elements: the wide tile spilled there
+  const bool narrow = !xal || (C + 31) / 32 * 32 < (C + 63) / 64 * 64;
+  if (R == 1)
+    return narrow ? choose_ring_rs<1, 7, true>(g, xal, gal, strip_rows)
+                  : choose_ring_rs<1, 7, false>(g, xal, gal, strip_rows);
+  if (R == 7)
+    return narrow ? choose_ring_rs<7, 1, true>(g, xal, gal, strip_rows)
+                  : choose_ring_rs<7, 1, false>(g, xal, gal, strip_rows);
+  return narrow ? choose_ring_rs<3, 3, true>(g, xal, gal, strip_rows)
+                : choose_ring_rs<3, 3, false>(g, xal, gal, strip_rows);
+}
+
+std::string tap_bwdw_ring_kernel_name(int64_t N, int64_t C, int64_t K,
+                                      int64_t H, int64_t W, int64_t R,
+                                      int64_t S, int64_t ph, int64_t pw) {
+  return choose_ring(N, C, K, H, W, R, S, ph, pw, true, true, 0).label;
+}
+
+// tap_bwd_weight's contract on tap_bwdw_ring_kernel.
+torch::Tensor tap_bwd_weight_ring(torch::Tensor go, torch::Tensor x, int64_t R,
+                                  int64_t S, int64_t ph, int64_t pw,
+                                  c10::optional<torch::Tensor> out,
+                                  int64_t strip_rows) {
+  TORCH_CHECK(go.is_cuda() && x.is_cuda() && go.get_device() == x.get_device(),
+              "tap_bwd_weight_ring: go and x must be on one GPU");
+  TORCH_CHECK(go.dim() == 4 && x.dim() == 4 && go.is_contiguous() &&
+                  x.is_contiguous(),
+              "tap_bwd_weight_ring: go and x must be contiguous 4-d tensors");
+  TORCH_CHECK(go.scalar_type() == torch::kBFloat16 &&
+                  x.scalar_type() == torch::kBFloat16,
+              "tap_bwd_weight_ring: bf16 only");
+  const RingChoice ch = choose_ring(
+      x.size(0), x.size(1), go.size(1), x.size(2), x.size(3), R, S, ph, pw,
+      ((uintptr_t)x.data_ptr() & 15) == 0, ((uintptr_t)go.data_ptr() & 15) == 0,
+      strip_rows);
+  const RingGeom& g = ch.g;
+  TORCH_CHECK(go.size(0) == g.N && go.size(2) == g.OH && go.size(3) == g.OW,
+              "tap_bwd_weight_ring: go is not the gradient of this convolution");
+  const int64_t numel = (int64_t)g.K * g.C * R * S;
+  torch::Tensor gw;
+  if (out.has_value()) {
+    gw = *out;
+    TORCH_CHECK(gw.is_cuda() && gw.get_device() == go.get_device() &&
+                    gw.scalar_type() == torch::kFloat && gw.is_contiguous() &&
+                    gw.numel() == numel,
+                "tap_bwd_weight_ring: out must be a contiguous fp32 tensor of "
+                "K*C*R*S elements on go's device");
+  } else {
+    gw = torch::zeros({numel}, x.options().dtype(torch::kFloat));
+  }
+  TORCH_CHECK(ch.blocks < (1LL << 31), "tap_bwd_weight_ring: grid too large");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(ch.kern, dim3((uint32_t)ch.blocks), dim3(256), 0,
+                     stream.stream(), (const unsigned short*)go.data_ptr(),
+                     (const unsigned short*)x.data_ptr(), gw.data_ptr<float>(),
+                     g);
+  return gw.view({(int64_t)g.K, (int64_t)g.C, R, S});
+}
+
 }  // namespace conv_tap
 
 void register_conv_tap(pybind11::module_& m) {
@@ -1031,4 +1388,15 @@ void register_conv_tap(pybind11::module_& m) {
   m.def("tap_bwdw_kernel_name", &conv_tap::tap_bwdw_kernel_name,
         "label of the kernel tap_bwd_weight launches for (N, C, K, H, W, R, S, "
         "ph, pw); no tensor, no HIP call");
+  m.def("tap_bwd_weight_ring", &conv_tap::tap_bwd_weight_ring,
+        pybind11::arg("go"), pybind11::arg("x"), pybind11::arg("R"),
+        pybind11::arg("S"), pybind11::arg("ph"), pybind11::arg("pw"),
+        pybind11::arg("out") = pybind11::none(),
+        pybind11::arg("strip_rows") = 0,
+        "tap_bwd_weight on the rolling-window kernel: a block walks a strip "
+        "of output rows and stages only the new rows of a step; strip_rows > 0 "
+        "overrides the chooser's strip length");
+  m.def("tap_bwdw_ring_kernel_name", &conv_tap::tap_bwdw_ring_kernel_name,
+        "label of the kernel tap_bwd_weight_ring launches for (N, C, K, H, W, "
+        "R, S, ph, pw); no tensor, no HIP call");
 }

@@ -38,7 +38,12 @@ Kernel families (csrc/):
   sink). Opt-in on top of the first switch: MPI4DL_TAPCONV_WGRAD=1 sends
   the weight-grad of every problem that MPI4DL_TAPCONV=1 routes to
   ge.tap_bwd_weight; alone it changes nothing (PERF_NOTES, "Tap-shift
-  weight gradient").
+  weight gradient"). MPI4DL_TAPCONV_WGRAD=ring sends it to
+  ge.tap_bwd_weight_ring instead: tap_bwdw_ring_kernel, the same GEMM on a
+  32 x 64 (or 32 x 32) channel tile, a block walking a strip of output
+  rows with the x rows in an LDS ring, so a step stages only its new rows,
+  two steps ahead, and two blocks fit a CU (PERF_NOTES, "Tap-shift weight
+  gradient, rolling window").
 
 Per-shape, per-LEG policy (all crossovers measured on MI355X —
 profiles/PERF_NOTES.md): stride-2 1x1s, K<=64 1x1s, stems, wide
@@ -51,12 +56,12 @@ F.conv2d/MIOpen. MPI4DL_NATIVE_CONV=0 disables all native paths,
 
 The per-leg policy is written once, in ``conv_plan``: a pure function
 of the problem's integers and the MPI4DL_PW_BLASLT,
-MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1 and MPI4DL_TAPCONV_WGRAD=1
+MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1 and MPI4DL_TAPCONV_WGRAD=1|ring
 switches. ``ConvFn`` executes the plan and decides nothing itself; which
 kernel a native route then launches is the extension's choice
 (``conv_fwd_kernel_name``, ``pw_kernel_name``, ``pw_bwdw_kernel_name``,
-``wino_kernel_name``, ``tap_kernel_name``, ``tap_bwdw_kernel_name``
-answer it for a plan's problems).
+``wino_kernel_name``, ``tap_kernel_name``, ``tap_bwdw_kernel_name``,
+``tap_bwdw_ring_kernel_name`` answer it for a plan's problems).
 """
 
 from __future__ import annotations
@@ -113,8 +118,11 @@ def _tap_on():
     return os.environ.get("MPI4DL_TAPCONV", "0") == "1"
 
 
-def _tap_wgrad_on():
-    return os.environ.get("MPI4DL_TAPCONV_WGRAD", "0") == "1"
+def _tap_wgrad_mode():
+    """MPI4DL_TAPCONV_WGRAD as conv_plan's ``tap_wgrad``: True for "1",
+    "ring" for "ring", False for anything else."""
+    v = os.environ.get("MPI4DL_TAPCONV_WGRAD", "0")
+    return "ring" if v == "ring" else v == "1"
 
 
 def _tap_ok(H, W, R, S, sh, sw, ph, pw):
@@ -154,6 +162,8 @@ class Leg(NamedTuple):
       tap_bwd_weight         ge.tap_bwd_weight; problem =
                              tap_bwdw_kernel_name's (N, C, K, H, W, R, S,
                              ph, pw), the forward convolution's
+      tap_bwd_weight_ring    ge.tap_bwd_weight_ring; problem =
+                             tap_bwdw_ring_kernel_name's, the same nine
     """
 
     route: str
@@ -172,8 +182,9 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
     and the problem that route hands to its binding. ``blaslt`` defaults
     to the MPI4DL_PW_BLASLT switch, ``winograd`` to
     MPI4DL_WINOGRAD == "fused", ``tap`` to MPI4DL_TAPCONV == "1" and
-    ``tap_wgrad`` (looked at only where ``tap`` routes the problem) to
-    MPI4DL_TAPCONV_WGRAD == "1"; nothing else is read."""
+    ``tap_wgrad`` (looked at only where ``tap`` routes the problem; True,
+    False or "ring") to MPI4DL_TAPCONV_WGRAD == "1" or "ring"; nothing else
+    is read."""
     if blaslt is None:
         blaslt = _blaslt_on()
     if winograd is None:
@@ -226,13 +237,19 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
         # opt-in tap-shift kernel: forward, and the data-grad as the same
         # kernel on go with the complementary pads; the weight-grad keeps
         # its kernel unless the second switch sends it to tap_bwd_weight
+        # or, as "ring", to tap_bwd_weight_ring
         if tap_wgrad is None:
-            tap_wgrad = _tap_wgrad_on()
+            tap_wgrad = _tap_wgrad_mode()
+        if tap_wgrad not in (True, False, "ring"):
+            raise ValueError(f"tap_wgrad must be a bool or 'ring', "
+                             f"got {tap_wgrad!r}")
+        tapw = (N, C, K, H, W, R, S, ph, pw)
         return ConvPlan(
             Leg("tap_fwd", (C, K, H, W, R, S, ph, pw)),
             Leg("tap_fwd", (K, C, OH, OW, R, S, R - 1 - ph, S - 1 - pw)),
-            (Leg("tap_bwd_weight", (N, C, K, H, W, R, S, ph, pw))
-             if tap_wgrad else Leg("conv_bwd_weight", fwd)),
+            (Leg("tap_bwd_weight_ring", tapw) if tap_wgrad == "ring"
+             else Leg("tap_bwd_weight", tapw) if tap_wgrad
+             else Leg("conv_bwd_weight", fwd)),
         )
     if (sh, sw) == (1, 1):
         # stride-1 data-grad = the forward kernel on C<->K transposed,
@@ -253,15 +270,14 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
 class ConvFn(torch.autograd.Function):
     """Executes ``conv_plan``. The plan is made once, in forward, and
     kept on ctx: backward reads none of MPI4DL_PW_BLASLT,
-    MPI4DL_WINOGRAD and MPI4DL_TAPCONV again, so a change of a variable
-    between a forward and its backward is ignored.
+    MPI4DL_WINOGRAD, MPI4DL_TAPCONV and MPI4DL_TAPCONV_WGRAD again, so a
+    change of a variable between a forward and its backward is ignored.
 
     Weight gradient: the routes that run our own kernels (pw_bwdw,
-    pw_bwdw_sub, conv_bwd_weight, tap_bwd_weight) add it straight into
-    ``w.grad`` when
-    ``grad_sink(w)`` allows, and backward then returns None for ``w``;
-    otherwise, and on the bmm route, it is returned for autograd to
-    accumulate."""
+    pw_bwdw_sub, conv_bwd_weight, tap_bwd_weight, tap_bwd_weight_ring) add
+    it straight into ``w.grad`` when ``grad_sink(w)`` allows, and backward
+    then returns None for ``w``; otherwise, and on the bmm route, it is
+    returned for autograd to accumulate."""
 
     @staticmethod
     def forward(ctx, x, w, bias, sh, sw, ph, pw):
@@ -318,6 +334,8 @@ class ConvFn(torch.autograd.Function):
                 gw = ge.conv_bwd_weight(go, xb, R, S, sh, sw, ph, pw, *out)
             elif gw_route == "tap_bwd_weight":
                 gw = ge.tap_bwd_weight(go, xb, R, S, ph, pw, *out)
+            elif gw_route == "tap_bwd_weight_ring":
+                gw = ge.tap_bwd_weight_ring(go, xb, R, S, ph, pw, *out)
             else:
                 xs = (xb if gw_route == "pw_bwdw"
                       else xb[:, :, ::sh, ::sw].contiguous())
