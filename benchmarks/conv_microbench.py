@@ -155,22 +155,25 @@ def tap_ab(args):
 def tap_bwdw_ab(args):
     """The shapes of --tap, weight-gradient leg only: the tap-shift kernel
     (ge.tap_bwd_weight), its rolling-window variant (ge.tap_bwd_weight_ring),
-    our general kernel (ge.conv_bwd_weight) and MIOpen
+    its pixel-major variant (ge.tap_bwd_weight_px), our general kernel (ge.conv_bwd_weight) and MIOpen
     (torch.nn.grad.conv2d_weight on bf16 tensors). Same protocol as --tap:
     all variants warmed up, five alternating rounds, the median round.
-    Ratios are MIOpen's time over the variant's."""
+    Ratios are MIOpen's time over the variant's; "px vs ring" is ring's time
+    over px's."""
     from mpi4dl_amd.ops import backend
 
     ge = backend.ext()
-    names = ("ring", "tap", "bwdw", "miopen")
+    names = ("px", "ring", "tap", "bwdw", "miopen")
     print(f"{'shape':<34}" + "".join(f"{n:>11}" for n in names)
-          + "   ring/tap/bwdw vs miopen  tap vs bwdw  ring vs tap  winner")
+          + "   px/ring/tap/bwdw vs miopen  tap vs bwdw  ring vs tap"
+          "  px vs ring  winner")
     for C, hw, R, S in TAP_SHAPES:
         ph, pw = R // 2, S // 2
         N = args.batch
         x = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
         go = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
         fns = {
+            "px": lambda: ge.tap_bwd_weight_px(go, x, R, S, ph, pw),
             "ring": lambda: ge.tap_bwd_weight_ring(go, x, R, S, ph, pw),
             "tap": lambda: ge.tap_bwd_weight(go, x, R, S, ph, pw),
             "bwdw": lambda: ge.conv_bwd_weight(go, x, R, S, 1, 1, ph, pw),
@@ -187,16 +190,18 @@ def tap_bwdw_ab(args):
         t = {n: sorted(v)[len(v) // 2] for n, v in rounds.items()}
         ref = fns["miopen"]().float()
         rel = {n: ((fns[n]() - ref).abs().max().item()
-                   / max(ref.abs().max().item(), 1e-3)) for n in names[:2]}
+                   / max(ref.abs().max().item(), 1e-3)) for n in names[:3]}
         tag = f"C{C}->K{C} {hw}x{hw} k{R}x{S} N{N}"
         print(f"{tag:<34}"
               + "".join(f"{t[n]:9.3f}ms" for n in names) + "   "
-              + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:3])
+              + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:4])
               + f"  {t['bwdw'] / t['tap']:5.2f}x  {t['tap'] / t['ring']:5.2f}x"
-              f"  {min(t, key=t.get):<7}"
-              f"[{ge.tap_bwdw_ring_kernel_name(N, C, C, hw, hw, R, S, ph, pw)}, "
+              f"  {t['ring'] / t['px']:5.2f}x  {min(t, key=t.get):<7}"
+              f"[{ge.tap_bwdw_px_kernel_name(N, C, C, hw, hw, R, S, ph, pw)}, "
+              f"{ge.tap_bwdw_ring_kernel_name(N, C, C, hw, hw, R, S, ph, pw)}, "
               f"{ge.tap_bwdw_kernel_name(N, C, C, hw, hw, R, S, ph, pw)}]"
-              f"  ring relerr {rel['ring']:.3g} tap relerr {rel['tap']:.3g}",
+              f"  px relerr {rel['px']:.3g} ring relerr {rel['ring']:.3g}"
+              f" tap relerr {rel['tap']:.3g}",
               flush=True)
 
 

@@ -151,6 +151,47 @@
 //   wherever x is staged by elements (W % 8 != 0 or an unaligned base): the
 //   three of the wide tile's six such instantiations spilled 96 - 352 bytes a
 //   lane, and none of the six is built.
+//
+// Weight gradient, pixel-major: tap_bwdw_px_kernel<R, S, XAL, GAL>
+//
+// The same GEMM with both operands staged as they lie in NCHW memory,
+// [channel][row][column]: the MFMA's k is 32 consecutive pixels of a row, and
+// a lane's 8 k values are 16 contiguous bytes of one channel, so there is no
+// transpose on the way into LDS (no v_perm) and none on the way out (plain
+// ds_read_b128, no ds_read_b64_tr_b16).
+//
+// * Block (256 threads): 128 output channels x 32 input channels x all taps
+//   and one strip, as in the ring kernel: a band of TW = 64 (1x7) or 32 (7x1,
+//   3x3) output columns over `rows` output rows, walked downwards in steps of
+//   TH = 2 (1x7) or 4 rows, 128 pixels between barriers. Where K <= 128, x is
+//   staged once per pixel for all of K; go is staged once per 32 channels of x.
+// * Waves: by go fragments, two each, with both x fragments and all taps:
+//   4 x R*S accumulator fragments (112 / 144 registers), 2 go reads and 2 x
+//   (R: 1 / 7 / 3) x (3 window reads, for 7x1 one) for 4 * R*S MFMAs a k-step.
+//   A wave whose go channels all lie past K only stages.
+// * Fragments: lane l reads channel (l & 15) at pixels p0 + 8 * (l >> 4) .. + 8.
+//   A row tap is a row offset in the address. Column taps: the patch starts
+//   PADL = 8 columns left of the band; per (x fragment, row, k-step) the lane
+//   reads the three aligned 8-pixel groups around its own, 12 registers, and
+//   tap s starts at element 8 + s - S/2 of them: an even start is four of the
+//   registers as they are, an odd one four v_alignbit_b32 (1x7: 16 of them for
+//   7 fragments, 3x3: 8 for 3). The starts are constants for the pad S/2; any
+//   other pw stages x by elements with the image moved S/2 - pw columns under
+//   the patch, so there is one compute loop per filter shape.
+// * LDS: a channel is its pixels rounded up to an odd number of 16-byte groups
+//   (go 272 bytes; x 336 / 656 / 592), so 16 consecutive channels at one pixel
+//   offset start on 16 different 16-byte spans of the 256-byte bank row. Two
+//   buffers of go (34816 B) and x: 91136 / 111616 / 107520 B, one block a CU.
+// * Staging (struct PxOperand): an item is 8 pixels of one row of one channel,
+//   one ds_write_b128. 16-byte path (W % 8 == 0, aligned base, for x also
+//   pw == S/2; OW % 8 == 0 for go): one 16-byte load an item, issued before the
+//   MFMAs of a step and masked and written after them, one barrier a step. By
+//   elements: eight clamped 2-byte loads and a mask per pixel, staged after the
+//   MFMAs without prefetch (held across them, 5 of the 8 such instantiations
+//   spilled). Zeros: pads, borders, go past OW and below the strip, channel
+//   tails. As above, x paired with zeroed go is real image data: finite inputs.
+// * Grid: as the ring kernel's, with the strip length chosen for at least
+//   2 x 256 blocks where the problem has that many steps.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -971,6 +1012,275 @@ __global__ __launch_bounds__(256, 2) void tap_bwdw_ring_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Weight gradient, pixel-major (header: "tap_bwdw_px_kernel")
+// ---------------------------------------------------------------------------
+
+template <int R, int S>
+struct PxTile {
+  using T = Tile<R, S>;
+  static constexpr int KB = 128, CB = 32;        // channels of go, of x
+  static constexpr int TH = S == 7 ? 2 : 4;      // 128 pixels a step
+  static constexpr int TW = T::TW;
+  static constexpr int PH = TH + R - 1;
+  static constexpr int PADL = T::PADL, PWL = T::PWL;
+  static constexpr int PWC = S / 2;              // the pad of the constant shifts
+  // shorts per channel: the pixels, up to an odd number of 16-byte groups
+  static constexpr int odd8(int n) { return (((n + 7) / 8) | 1) * 8; }
+  static constexpr int GSTR = odd8(TH * TW);
+  static constexpr int XSTR = odd8(PH * PWL);
+  static constexpr int GBUF = KB * GSTR;
+  static constexpr int BUF = GBUF + CB * XSTR;   // one step: go, then x
+  static constexpr int LDS_SHORTS = 2 * BUF;
+  static_assert(TW % 32 == 0, "a k-step is 32 pixels of one row");
+  static_assert(S == 1 || TW + 16 <= PWL, "the last window lies in the patch");
+  static_assert(LDS_SHORTS * 2 <= 160 * 1024, "LDS of one CU");
+};
+
+// One operand of a step: CH channels x ROWS x COLS pixels of an NCHW image,
+// staged as it lies in memory, [channel][row][column], CSTR shorts a channel.
+// An item is 8 consecutive pixels of one row of one channel, one
+// ds_write_b128; consecutive threads take consecutive groups of a row.
+// ALIGNED: one 16-byte load an item, issued by `load` and written by `commit`.
+// Otherwise `load` does nothing and `commit` stages item by item: eight 2-byte
+// loads with the column clamped into the row, a mask per pixel, the write. No
+// prefetch on that path: with its items held across the MFMAs five of the
+// eight such instantiations spilled.
+template <int CH, int ROWS, int COLS, int CSTR, bool ALIGNED>
+struct PxOperand {
+  static constexpr int G = COLS / 8;
+  static constexpr int ITEMS = CH * ROWS * G;
+  static constexpr int PT = (ITEMS + 255) / 256;  // items per thread
+  // channels c0 .. c0 + CH of an image of Cmax channels, HW elements each;
+  // rows below Hi and columns below Wi are inside
+  const unsigned short* img;
+  int HW, c0, Cmax, Hi, Wi;
+  int soff[ALIGNED ? PT : 1];  // offset in the channel plane; -1: outside
+  i32x4 rawv[ALIGNED ? PT : 1];
+
+  static __device__ __forceinline__ void split(int u, int& ch, int& row,
+                                               int& col) {
+    col = u % G * 8;
+    row = u / G % ROWS;
+    ch = u / (G * ROWS);
+  }
+  // clamped below Cmax: always inside the image (32-bit offsets from a uniform
+  // base: an image has fewer than 2^31 elements)
+  __device__ __forceinline__ const unsigned short* plane(int ch) const {
+    return img + (unsigned)((c0 + ch < Cmax ? c0 + ch : Cmax - 1) * HW);
+  }
+
+  // (row0, col0): image coordinates of row 0 and column 0 of the step.
+  // Nothing is read of the loads before `commit`.
+  __device__ __forceinline__ void load(int tid, int row0, int col0) {
+    if constexpr (ALIGNED) {
+#pragma unroll
+      for (int it = 0; it < PT; ++it) {
+        if (it * 256 + tid >= ITEMS) continue;
+        int ch, row, col;
+        split(it * 256 + tid, ch, row, col);
+        const int ih = row0 + row, iw = col0 + col;
+        // Wi % 8 == 0 and iw % 8 == 0: a group is wholly in or out
+        const bool ok = ih >= 0 && ih < Hi && iw >= 0 && iw < Wi;
+        soff[it] = ok ? ih * Wi + iw : -1;
+        rawv[it] = *(const i32x4*)(plane(ch) + (ok ? soff[it] : 0));
+      }
+    }
+  }
+
+  // pads, borders, the pixel tail and the channel tail become zeros here
+  __device__ __forceinline__ void commit(short* buf, int tid, int row0,
+                                         int col0) {
+    if constexpr (ALIGNED) {
+#pragma unroll
+      for (int it = 0; it < PT; ++it) {
+        if (it * 256 + tid >= ITEMS) continue;
+        int ch, row, col;
+        split(it * 256 + tid, ch, row, col);
+        const int m = soff[it] >= 0 && c0 + ch < Cmax ? -1 : 0;
+        i32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = rawv[it][j] & m;
+        *(i32x4*)(buf + ch * CSTR + row * COLS + col) = o;
+      }
+    } else {
+#pragma unroll 1
+      for (int u = tid; u < ITEMS; u += 256) {
+        int ch, row, col;
+        split(u, ch, row, col);
+        const int ih = row0 + row, iw = col0 + col;
+        const bool rok = ih >= 0 && ih < Hi && c0 + ch < Cmax;
+        const unsigned short* p = plane(ch) + (ih >= 0 && ih < Hi ? ih * Wi : 0);
+        unsigned v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int w = iw + e;
+          const unsigned raw = p[w < 0 ? 0 : w < Wi ? w : Wi - 1];
+          v[e] = rok && w >= 0 && w < Wi ? raw : 0u;
+        }
+        i32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (int)(v[2 * j] | (v[2 * j + 1] << 16));
+        *(i32x4*)(buf + ch * CSTR + row * COLS + col) = o;
+      }
+    }
+  }
+};
+
+template <int R, int S, bool XAL, bool GAL>
+__global__ __launch_bounds__(256) void tap_bwdw_px_kernel(
+    const unsigned short* __restrict__ go, const unsigned short* __restrict__ x,
+    float* __restrict__ gw, RingGeom g) {
+  using T = PxTile<R, S>;
+  constexpr int RS = R * S, KB = T::KB, CB = T::CB;
+  constexpr int TH = T::TH, TW = T::TW, PWL = T::PWL;
+  constexpr int GSTR = T::GSTR, XSTR = T::XSTR;
+  constexpr int KFW = KB / 64, CF = CB / 16;  // go fragments of a wave, x's
+  constexpr int KPR = TW / 32;                // k-steps (32 pixels) per row
+  constexpr int KS = TH * KPR;                // k-steps per step
+
+  __shared__ __attribute__((aligned(16))) short lds[T::LDS_SHORTS];
+
+  // block -> (k tile, c tile, strip, band, image); XCD-aware bijective swizzle
+  // as in tap_bwdw_ring_kernel: the output tiles of a strip are consecutive, so
+  // they share an L2
+  const int nwg = gridDim.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  const int xcd = blockIdx.x & 7, sub = blockIdx.x >> 3;
+  int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + sub;
+  if (bid >= nwg) bid = blockIdx.x;  // never taken: the mapping is bijective
+  const int k0 = (bid % g.k_tiles) * KB;
+  bid /= g.k_tiles;
+  const int c0 = (bid % g.c_tiles) * CB;
+  bid /= g.c_tiles;
+  const int oh_b = (bid % g.strips_per_band) * g.rows;
+  bid /= g.strips_per_band;
+  const int ow0 = (bid % g.col_bands) * TW;
+  const int n = bid / g.col_bands;
+  const int oh_e = oh_b + g.rows < g.OH ? oh_b + g.rows : g.OH;
+  const int steps = (oh_e - oh_b + TH - 1) / TH;  // >= 1: oh_b < OH
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int HW = g.H * g.W, OHW = g.OH * g.OW;
+  const unsigned short* gon = go + (int64_t)n * g.K * OHW;
+  const unsigned short* xn = x + (int64_t)n * g.C * HW;
+
+  PxOperand<KB, TH, TW, GSTR, GAL> sg{gon, OHW, k0, g.K, oh_e, g.OW};
+  PxOperand<CB, T::PH, PWL, XSTR, XAL> sx{xn, HW, c0, g.C, g.H, g.W};
+  // patch column 0: PADL left of the band for the pad PWC of the constant
+  // shifts; any other pad moves the image under the patch (by elements only).
+  // go is zero below the strip (oh_e).
+  const int xcol0 = ow0 - T::PADL + T::PWC - g.pw;
+  auto stage_load = [&](int i) {
+    sg.load(tid, oh_b + i * TH, ow0);
+    sx.load(tid, oh_b + i * TH - g.ph, xcol0);
+  };
+  auto stage_commit = [&](int i) {
+    short* b = lds + (i & 1) * T::BUF;
+    sg.commit(b, tid, oh_b + i * TH, ow0);
+    sx.commit(b + T::GBUF, tid, oh_b + i * TH - g.ph, xcol0);
+  };
+
+  // fragment addresses of k-step 0: lane l holds channel (l & 15) of its
+  // fragment at pixels 8 * (l >> 4) .. + 8, for x one group left of them
+  const int aoff = (wid * KFW * 16 + (lane & 15)) * GSTR + ((lane >> 4) << 3);
+  const int boff = (lane & 15) * XSTR + ((lane >> 4) << 3);
+  // a wave whose go channels all lie past K stages and waits, nothing else
+  const bool live = k0 + wid * KFW * 16 < g.K;
+
+  f32x4 acc[KFW][CF][RS];
+#pragma unroll
+  for (int kf = 0; kf < KFW; ++kf)
+#pragma unroll
+    for (int cf = 0; cf < CF; ++cf)
+#pragma unroll
+      for (int t = 0; t < RS; ++t)
+        acc[kf][cf][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  stage_load(0);
+  stage_commit(0);
+  __syncthreads();
+
+  for (int i = 0; i < steps; ++i) {
+    const bool more = i + 1 < steps;
+    if (more) stage_load(i + 1);
+    const short* gb = lds + (i & 1) * T::BUF + aoff;
+    const short* xb = lds + (i & 1) * T::BUF + T::GBUF + boff;
+    if (live) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const int row = ks / KPR, col = (ks % KPR) * 32;
+        s16x8 a[KFW];
+#pragma unroll
+        for (int kf = 0; kf < KFW; ++kf)
+          a[kf] = *(const s16x8*)(gb + kf * 16 * GSTR + row * TW + col);
+#pragma unroll
+        for (int cf = 0; cf < CF; ++cf)
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            const short* p = xb + cf * 16 * XSTR + (row + r) * PWL + col;
+            if constexpr (S == 1) {
+              const s16x8 b = *(const s16x8*)p;
+#pragma unroll
+              for (int kf = 0; kf < KFW; ++kf)
+                acc[kf][cf][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    a[kf], b, acc[kf][cf][r], 0, 0, 0);
+            } else {
+              // the 24 pixels around the fragment; tap s starts at element
+              // 8 + s - PWC: even, four registers as they are; odd, four
+              // v_alignbit
+              unsigned d[12];
+#pragma unroll
+              for (int q = 0; q < 3; ++q) {
+                const i32x4 v = *(const i32x4*)(p + q * 8);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d[q * 4 + j] = (unsigned)v[j];
+              }
+#pragma unroll
+              for (int s = 0; s < S; ++s) {
+                constexpr int E0 = 8 - T::PWC;
+                const int m = (E0 + s) / 2;
+                i32x4 o;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                  o[j] = (int)((E0 + s) % 2 == 0
+                                   ? d[m + j]
+                                   : __builtin_amdgcn_alignbit(d[m + j + 1],
+                                                               d[m + j], 16));
+                const s16x8 b = __builtin_bit_cast(s16x8, o);
+#pragma unroll
+                for (int kf = 0; kf < KFW; ++kf)
+                  acc[kf][cf][r * S + s] =
+                      __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                          a[kf], b, acc[kf][cf][r * S + s], 0, 0, 0);
+              }
+            }
+          }
+      }
+    }
+    if (more) stage_commit(i + 1);
+    __syncthreads();
+  }
+
+  // D layout of the MFMA: row (lane >> 4)*4 + reg (k), column lane & 15 (c)
+#pragma unroll
+  for (int kf = 0; kf < KFW; ++kf)
+#pragma unroll
+    for (int cf = 0; cf < CF; ++cf) {
+      const int c = c0 + cf * 16 + (lane & 15);
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int k = k0 + (wid * KFW + kf) * 16 + ((lane >> 4) << 2) + reg;
+        if (k >= g.K || c >= g.C) continue;
+        float* dst = gw + ((int64_t)k * g.C + c) * RS;
+#pragma unroll
+        for (int t = 0; t < RS; ++t) atomicAdd(dst + t, acc[kf][cf][t][reg]);
+      }
+    }
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -1365,6 +1675,113 @@ torch::Tensor tap_bwd_weight_ring(torch::Tensor go, torch::Tensor x, int64_t R,
   return gw.view({(int64_t)g.K, (int64_t)g.C, R, S});
 }
 
+// ---- weight gradient, pixel-major -------------------------------------------
+
+// The launch of a pixel-major problem: the only place that decides the
+// instantiation, the strip length and the grid.
+template <int R, int S>
+static RingChoice choose_px_rs(RingGeom g, bool xal, bool gal,
+                               int64_t strip_rows) {
+  using T = PxTile<R, S>;
+  constexpr int64_t GRID = 2 * 256;  // one resident block per CU, two rounds
+  g.col_bands = (g.OW + T::TW - 1) / T::TW;
+  g.k_tiles = (g.K + T::KB - 1) / T::KB;
+  g.c_tiles = (g.C + T::CB - 1) / T::CB;
+  const int64_t ot = (int64_t)g.k_tiles * g.c_tiles;
+  const int64_t bands = (int64_t)g.N * g.col_bands;
+  const int64_t row_steps = (g.OH + T::TH - 1) / T::TH;  // steps of one band
+  // as choose_ring_rs: `need` strips a band make at least GRID blocks
+  // wherever a band has that many steps
+  int64_t spb = (strip_rows + T::TH - 1) / T::TH;
+  if (strip_rows <= 0) {
+    const int64_t need = (GRID + ot * bands - 1) / (ot * bands);
+    spb = row_steps / need;
+  }
+  spb = std::min(std::max<int64_t>(spb, 1), row_steps);
+  g.rows = (int)(spb * T::TH);
+  g.strips_per_band = (int)((row_steps + spb - 1) / spb);
+  const int64_t blocks = ot * bands * g.strips_per_band;
+  // the constant shifts are those of pad S / 2: any other pad stages x by
+  // elements, at a column offset
+  xal = xal && g.pw == T::PWC;
+  const RingKern k = xal ? (gal ? tap_bwdw_px_kernel<R, S, true, true>
+                                : tap_bwdw_px_kernel<R, S, true, false>)
+                         : (gal ? tap_bwdw_px_kernel<R, S, false, true>
+                                : tap_bwdw_px_kernel<R, S, false, false>);
+  return {k, g, blocks,
+          "tap_bwdw_px<" + std::to_string(R) + "x" + std::to_string(S) + "," +
+              std::to_string(T::KB) + "x" + std::to_string(T::CB) + ",rows" +
+              std::to_string(g.rows) + "," + (xal ? "x16" : "xel") + "," +
+              (gal ? "go16" : "goel") + ">"};
+}
+
+static RingChoice choose_px(int64_t N, int64_t C, int64_t K, int64_t H,
+                            int64_t W, int64_t R, int64_t S, int64_t ph,
+                            int64_t pw, bool x_aligned, bool go_aligned,
+                            int64_t strip_rows) {
+  check_problem(N, C, K, H, W, R, S, ph, pw, "tap_bwd_weight_px");
+  RingGeom g;
+  g.N = (int)N; g.C = (int)C; g.K = (int)K; g.H = (int)H; g.W = (int)W;
+  g.ph = (int)ph; g.pw = (int)pw;
+  g.OH = g.H + 2 * g.ph - (int)R + 1;
+  g.OW = g.W + 2 * g.pw - (int)S + 1;
+  // the kernel addresses one image of x and of go with 32-bit offsets
+  TORCH_CHECK(C * H * W < (1LL << 31) && K * g.OH * g.OW < (1LL << 31),
+              "tap_bwd_weight_px: problem too large");
+  const bool xal = x_aligned && g.W % 8 == 0;
+  const bool gal = go_aligned && g.OW % 8 == 0;
+  if (R == 1) return choose_px_rs<1, 7>(g, xal, gal, strip_rows);
+  if (R == 7) return choose_px_rs<7, 1>(g, xal, gal, strip_rows);
+  return choose_px_rs<3, 3>(g, xal, gal, strip_rows);
+}
+
+std::string tap_bwdw_px_kernel_name(int64_t N, int64_t C, int64_t K, int64_t H,
+                                    int64_t W, int64_t R, int64_t S,
+                                    int64_t ph, int64_t pw) {
+  return choose_px(N, C, K, H, W, R, S, ph, pw, true, true, 0).label;
+}
+
+// tap_bwd_weight's contract on tap_bwdw_px_kernel.
+torch::Tensor tap_bwd_weight_px(torch::Tensor go, torch::Tensor x, int64_t R,
+                                int64_t S, int64_t ph, int64_t pw,
+                                c10::optional<torch::Tensor> out,
+                                int64_t strip_rows) {
+  TORCH_CHECK(go.is_cuda() && x.is_cuda() && go.get_device() == x.get_device(),
+              "tap_bwd_weight_px: go and x must be on one GPU");
+  TORCH_CHECK(go.dim() == 4 && x.dim() == 4 && go.is_contiguous() &&
+                  x.is_contiguous(),
+              "tap_bwd_weight_px: go and x must be contiguous 4-d tensors");
+  TORCH_CHECK(go.scalar_type() == torch::kBFloat16 &&
+                  x.scalar_type() == torch::kBFloat16,
+              "tap_bwd_weight_px: bf16 only");
+  const RingChoice ch = choose_px(
+      x.size(0), x.size(1), go.size(1), x.size(2), x.size(3), R, S, ph, pw,
+      ((uintptr_t)x.data_ptr() & 15) == 0, ((uintptr_t)go.data_ptr() & 15) == 0,
+      strip_rows);
+  const RingGeom& g = ch.g;
+  TORCH_CHECK(go.size(0) == g.N && go.size(2) == g.OH && go.size(3) == g.OW,
+              "tap_bwd_weight_px: go is not the gradient of this convolution");
+  const int64_t numel = (int64_t)g.K * g.C * R * S;
+  torch::Tensor gw;
+  if (out.has_value()) {
+    gw = *out;
+    TORCH_CHECK(gw.is_cuda() && gw.get_device() == go.get_device() &&
+                    gw.scalar_type() == torch::kFloat && gw.is_contiguous() &&
+                    gw.numel() == numel,
+                "tap_bwd_weight_px: out must be a contiguous fp32 tensor of "
+                "K*C*R*S elements on go's device");
+  } else {
+    gw = torch::zeros({numel}, x.options().dtype(torch::kFloat));
+  }
+  TORCH_CHECK(ch.blocks < (1LL << 31), "tap_bwd_weight_px: grid too large");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(ch.kern, dim3((uint32_t)ch.blocks), dim3(256), 0,
+                     stream.stream(), (const unsigned short*)go.data_ptr(),
+                     (const unsigned short*)x.data_ptr(), gw.data_ptr<float>(),
+                     g);
+  return gw.view({(int64_t)g.K, (int64_t)g.C, R, S});
+}
+
 }  // namespace conv_tap
 
 void register_conv_tap(pybind11::module_& m) {
@@ -1398,5 +1815,16 @@ void register_conv_tap(pybind11::module_& m) {
         "overrides the chooser's strip length");
   m.def("tap_bwdw_ring_kernel_name", &conv_tap::tap_bwdw_ring_kernel_name,
         "label of the kernel tap_bwd_weight_ring launches for (N, C, K, H, W, "
+        "R, S, ph, pw); no tensor, no HIP call");
+  m.def("tap_bwd_weight_px", &conv_tap::tap_bwd_weight_px, pybind11::arg("go"),
+        pybind11::arg("x"), pybind11::arg("R"), pybind11::arg("S"),
+        pybind11::arg("ph"), pybind11::arg("pw"),
+        pybind11::arg("out") = pybind11::none(),
+        pybind11::arg("strip_rows") = 0,
+        "tap_bwd_weight on the pixel-major kernel: go and x staged as they "
+        "lie in memory, column taps shifted in registers; strip_rows > 0 "
+        "overrides the chooser's strip length");
+  m.def("tap_bwdw_px_kernel_name", &conv_tap::tap_bwdw_px_kernel_name,
+        "label of the kernel tap_bwd_weight_px launches for (N, C, K, H, W, "
         "R, S, ph, pw); no tensor, no HIP call");
 }

@@ -43,7 +43,12 @@ Kernel families (csrc/):
   32 x 64 (or 32 x 32) channel tile, a block walking a strip of output
   rows with the x rows in an LDS ring, so a step stages only its new rows,
   two steps ahead, and two blocks fit a CU (PERF_NOTES, "Tap-shift weight
-  gradient, rolling window").
+  gradient, rolling window"). MPI4DL_TAPCONV_WGRAD=px sends it to
+  ge.tap_bwd_weight_px: tap_bwdw_px_kernel, which stages go and x as they
+  lie in memory, pixel-innermost (a 16-byte copy, no transpose in or out
+  of LDS), on a 128 x 32 channel tile, and takes the column taps as
+  register shifts of a 24-pixel window (PERF_NOTES, "Tap-shift weight
+  gradient, pixel-major").
 
 Per-shape, per-LEG policy (all crossovers measured on MI355X —
 profiles/PERF_NOTES.md): stride-2 1x1s, K<=64 1x1s, stems, wide
@@ -56,12 +61,13 @@ F.conv2d/MIOpen. MPI4DL_NATIVE_CONV=0 disables all native paths,
 
 The per-leg policy is written once, in ``conv_plan``: a pure function
 of the problem's integers and the MPI4DL_PW_BLASLT,
-MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1 and MPI4DL_TAPCONV_WGRAD=1|ring
+MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1 and MPI4DL_TAPCONV_WGRAD=1|ring|px
 switches. ``ConvFn`` executes the plan and decides nothing itself; which
 kernel a native route then launches is the extension's choice
 (``conv_fwd_kernel_name``, ``pw_kernel_name``, ``pw_bwdw_kernel_name``,
 ``wino_kernel_name``, ``tap_kernel_name``, ``tap_bwdw_kernel_name``,
-``tap_bwdw_ring_kernel_name`` answer it for a plan's problems).
+``tap_bwdw_ring_kernel_name``, ``tap_bwdw_px_kernel_name`` answer it for a
+plan's problems).
 """
 
 from __future__ import annotations
@@ -120,9 +126,9 @@ def _tap_on():
 
 def _tap_wgrad_mode():
     """MPI4DL_TAPCONV_WGRAD as conv_plan's ``tap_wgrad``: True for "1",
-    "ring" for "ring", False for anything else."""
+    "ring" for "ring", "px" for "px", False for anything else."""
     v = os.environ.get("MPI4DL_TAPCONV_WGRAD", "0")
-    return "ring" if v == "ring" else v == "1"
+    return v if v in ("ring", "px") else v == "1"
 
 
 def _tap_ok(H, W, R, S, sh, sw, ph, pw):
@@ -164,6 +170,8 @@ class Leg(NamedTuple):
                              ph, pw), the forward convolution's
       tap_bwd_weight_ring    ge.tap_bwd_weight_ring; problem =
                              tap_bwdw_ring_kernel_name's, the same nine
+      tap_bwd_weight_px      ge.tap_bwd_weight_px; problem =
+                             tap_bwdw_px_kernel_name's, the same nine
     """
 
     route: str
@@ -183,8 +191,8 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
     to the MPI4DL_PW_BLASLT switch, ``winograd`` to
     MPI4DL_WINOGRAD == "fused", ``tap`` to MPI4DL_TAPCONV == "1" and
     ``tap_wgrad`` (looked at only where ``tap`` routes the problem; True,
-    False or "ring") to MPI4DL_TAPCONV_WGRAD == "1" or "ring"; nothing else
-    is read."""
+    False, "ring" or "px") to MPI4DL_TAPCONV_WGRAD == "1", "ring" or "px";
+    nothing else is read."""
     if blaslt is None:
         blaslt = _blaslt_on()
     if winograd is None:
@@ -237,17 +245,18 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
         # opt-in tap-shift kernel: forward, and the data-grad as the same
         # kernel on go with the complementary pads; the weight-grad keeps
         # its kernel unless the second switch sends it to tap_bwd_weight
-        # or, as "ring", to tap_bwd_weight_ring
+        # or, as "ring" or "px", to tap_bwd_weight_ring or tap_bwd_weight_px
         if tap_wgrad is None:
             tap_wgrad = _tap_wgrad_mode()
-        if tap_wgrad not in (True, False, "ring"):
-            raise ValueError(f"tap_wgrad must be a bool or 'ring', "
+        if tap_wgrad not in (True, False, "ring", "px"):
+            raise ValueError(f"tap_wgrad must be a bool, 'ring' or 'px', "
                              f"got {tap_wgrad!r}")
         tapw = (N, C, K, H, W, R, S, ph, pw)
         return ConvPlan(
             Leg("tap_fwd", (C, K, H, W, R, S, ph, pw)),
             Leg("tap_fwd", (K, C, OH, OW, R, S, R - 1 - ph, S - 1 - pw)),
             (Leg("tap_bwd_weight_ring", tapw) if tap_wgrad == "ring"
+             else Leg("tap_bwd_weight_px", tapw) if tap_wgrad == "px"
              else Leg("tap_bwd_weight", tapw) if tap_wgrad
              else Leg("conv_bwd_weight", fwd)),
         )
@@ -274,9 +283,9 @@ class ConvFn(torch.autograd.Function):
     change of a variable between a forward and its backward is ignored.
 
     Weight gradient: the routes that run our own kernels (pw_bwdw,
-    pw_bwdw_sub, conv_bwd_weight, tap_bwd_weight, tap_bwd_weight_ring) add
-    it straight into ``w.grad`` when ``grad_sink(w)`` allows, and backward
-    then returns None for ``w``; otherwise, and on the bmm route, it is
+    pw_bwdw_sub, conv_bwd_weight, tap_bwd_weight, tap_bwd_weight_ring,
+    tap_bwd_weight_px) add it straight into ``w.grad`` when ``grad_sink(w)``
+    allows, and backward then returns None for ``w``; otherwise, and on the bmm route, it is
     returned for autograd to accumulate."""
 
     @staticmethod
@@ -336,6 +345,8 @@ class ConvFn(torch.autograd.Function):
                 gw = ge.tap_bwd_weight(go, xb, R, S, ph, pw, *out)
             elif gw_route == "tap_bwd_weight_ring":
                 gw = ge.tap_bwd_weight_ring(go, xb, R, S, ph, pw, *out)
+            elif gw_route == "tap_bwd_weight_px":
+                gw = ge.tap_bwd_weight_px(go, xb, R, S, ph, pw, *out)
             else:
                 xs = (xb if gw_route == "pw_bwdw"
                       else xb[:, :, ::sh, ::sw].contiguous())
