@@ -91,38 +91,49 @@ TAP_SHAPES = (
      for r, s in ((1, 7), (7, 1))]
     + [(c, hw, 3, 3) for c, hw in WINO_SHAPES[:4]]
 )
+# (C = K, H, W): the tiles a 4-way spatial split of the 128² and 64² planes
+# hands one GPU; run at --batch and at N = 1, 1x7 and 7x1
+TAP_TILES = ((208, 64, 64), (416, 32, 32), (416, 64, 16))
 
 
 def tap_ab(args):
     """Stride-1 1x7 / 7x1 / 3x3, forward and data-grad legs: the tap-shift
-    kernel (ge.tap_fwd, filter pre-pass included), our direct kernel
-    (ge.conv_fwd; its data-grad includes the weight transpose and flip that
-    ConvFn does) and MIOpen. All variants are warmed up first; the timed
-    rounds then alternate between them, and the median round of each is
-    reported. Ratios are MIOpen's time over the variant's."""
+    kernel (ge.tap_fwd, filter pre-pass included), the same with the channels
+    split as its chooser says (split=-1: workspace allocation and reduce
+    kernel included), our direct kernel (ge.conv_fwd; its data-grad includes
+    the weight transpose and flip that ConvFn does) and MIOpen. All variants
+    are warmed up first; the timed rounds then alternate between them, and
+    the median round of each is reported. Ratios are MIOpen's time over the
+    variant's."""
     import torch.nn.functional as F
 
     from mpi4dl_amd.ops import backend
 
     ge = backend.ext()
-    names = ("tap", "direct", "miopen")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    names = ("tap", "split", "direct", "miopen")
     print(f"{'shape':<34}{'leg':<5}" + "".join(f"{n:>11}" for n in names)
-          + "   tap/direct vs miopen  winner")
-    for C, hw, R, S in TAP_SHAPES:
+          + "   tap/split/direct vs miopen  winner")
+    shapes = [(c, hw, hw, r, s, args.batch) for c, hw, r, s in TAP_SHAPES]
+    shapes += [(c, h, w, r, s, n) for n in sorted({args.batch, 1}, reverse=True)
+               for c, h, w in TAP_TILES for r, s in ((1, 7), (7, 1))]
+    for C, H, W, R, S, N in shapes:
         ph, pw = R // 2, S // 2
-        N = args.batch
-        x = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
-        go = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
+        x = torch.randn(N, C, H, W, device="cuda", dtype=torch.bfloat16)
+        go = torch.randn(N, C, H, W, device="cuda", dtype=torch.bfloat16)
         wb = (torch.randn(C, C, R, S, device="cuda") * 0.05).to(torch.bfloat16)
         legs = {
             "fwd": {
                 "tap": lambda: ge.tap_fwd(x, wb, None, ph, pw),
+                "split": lambda: ge.tap_fwd(x, wb, None, ph, pw, split=-1),
                 "direct": lambda: ge.conv_fwd(x, wb, None, 1, 1, ph, pw),
                 "miopen": lambda: F.conv2d(x, wb, padding=(ph, pw)),
             },
             "gx": {
                 "tap": lambda: ge.tap_fwd(go, wb, None, R - 1 - ph,
                                           S - 1 - pw, True),
+                "split": lambda: ge.tap_fwd(go, wb, None, R - 1 - ph,
+                                            S - 1 - pw, True, split=-1),
                 "direct": lambda: ge.conv_fwd(
                     go, wb.transpose(0, 1).flip(2, 3).contiguous(), None,
                     1, 1, R - 1 - ph, S - 1 - pw),
@@ -142,14 +153,21 @@ def tap_ab(args):
             ref = fns["miopen"]().float()
             rel = ((fns["tap"]().float() - ref).abs().max().item()
                    / max(ref.abs().max().item(), 1e-3))
-            tag = f"C{C}->K{C} {hw}x{hw} k{R}x{S} N{N}"
+            assert torch.equal(fns["split"](), fns["split"]())
+            srel = ((fns["split"]().float() - ref).abs().max().item()
+                    / max(ref.abs().max().item(), 1e-3))
+            sname, sc = ge.tap_split_kernel_name(N, C, C, H, W, R, S, ph, pw,
+                                                 cus)
+            tag = f"C{C}->K{C} {H}x{W} k{R}x{S} N{N}"
             print(f"{tag:<34}{leg:<5}"
                   + "".join(f"{t[n]:9.3f}ms" for n in names) + "   "
-                  + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:2])
+                  + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:3])
                   + f"  {min(t, key=t.get):<7}"
-                  f"[{ge.tap_kernel_name(C, C, hw, hw, R, S, ph, pw)}, "
-                  f"{ge.conv_fwd_kernel_name(C, C, hw, hw, R, S, 1, 1, ph, pw)}]"
-                  f"  tap relerr {rel:.3g}", flush=True)
+                  f"[{ge.tap_kernel_name(C, C, H, W, R, S, ph, pw)}, "
+                  f"{sname} sc{sc}, "
+                  f"{ge.conv_fwd_kernel_name(C, C, H, W, R, S, 1, 1, ph, pw)}]"
+                  f"  tap relerr {rel:.3g} split relerr {srel:.3g}",
+                  flush=True)
 
 
 def tap_bwdw_ab(args):

@@ -48,6 +48,34 @@
 // * No atomics, fixed summation order: bit-identical from run to run. No
 //   synchronisation, no host read, no allocation outside torch's allocator.
 //
+// Split channels: tap_fwd_split_kernel<R, S, MF, ALIGNED> and
+// tap_split_reduce_kernel, for grids that under-fill the device (a 64 x 64
+// plane at N = 2 is 128 - 160 blocks of the kernel above). Opt-in:
+// tap_fwd(split != 0).
+//
+// * The same body (tap_fwd_body: staging, tap addressing and fragment reads
+//   are one piece of code), on a grid SC times as large: the slice index is
+//   folded into the block index after the k tile. Slice sc runs the chunks
+//   [first(sc), first(sc + 1)) of the ceil(C/32), dealt evenly with the
+//   remainder to the earlier slices; SC <= chunks, so none is empty. Double
+//   buffering and the one-tap-ahead weight loads are per slice.
+// * Epilogue: the fp32 accumulators as they are, no bias, no rounding, to the
+//   workspace part[SC][N][K][OH][OW] (a torch allocation of the launch),
+//   through an fp32 [k][pixel] LDS image over the patch buffers, as many row
+//   fragments a pass as fit them (3 for 1x7, 4 otherwise), then 16-byte row
+//   stores where OW % 4 == 0, guarded element stores otherwise.
+// * tap_split_reduce_kernel: out = bf16(part[0] + ... + part[SC-1] + bias),
+//   added in that order in fp32: no atomics, bit-identical from run to run.
+//   A thread takes 8 elements with 16-byte loads and one 16-byte store where
+//   OH*OW % 8 == 0, one element otherwise.
+// * Chooser (tap_split_choice, the one place). With the unsplit kernel's MF,
+//   a grid of at least 2 blocks per CU stays unsplit: SC = 1. Otherwise MF is
+//   the unsplit chooser's but 4 in place of 7 (about 148 + 64 registers: two
+//   waves per SIMD, and 7 k tiles where MF = 7 has 4), and SC is the smallest
+//   of 1 .. min(chunks, 8) that reaches 2 blocks per CU, or the largest
+//   allowed if none does. If that SC is 1 the launch is the unsplit kernel
+//   with its own MF. A forced slice count uses the same MF.
+//
 // Weight gradient: tap_bwdw_kernel<R, S, XAL, GAL>
 //
 //   gw[k][c][r][s] += sum_{n,oh,ow} go[n][k][oh][ow] * x[n][c][oh-ph+r][ow-pw+s]
@@ -201,6 +229,8 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <tuple>
+#include <utility>
 
 namespace conv_tap {
 
@@ -221,6 +251,7 @@ struct TapGeom {
   int Kp, Cp;      // padded extents of Wt
   int row_blocks, col_blocks, k_tiles;
   int vec_out;     // 16-byte row stores are possible
+  int sc;          // channel slices (tap_fwd_split_kernel only)
 };
 
 // Tile geometry of a filter shape, shared by the kernel and the host.
@@ -278,11 +309,15 @@ __global__ __launch_bounds__(256) void tap_filter_kernel(
 // Main kernel
 // ---------------------------------------------------------------------------
 
-template <int R, int S, int MF, bool ALIGNED>
-__global__ __launch_bounds__(256) void tap_fwd_kernel(
+// The body of tap_fwd_kernel and of tap_fwd_split_kernel. SPLIT: the block
+// runs only its slice of the channel chunks and leaves its fp32 accumulators
+// in `part` (bias and out are not used); otherwise all chunks, and bias,
+// rounding and `out` as described above (`part` is not used).
+template <int R, int S, int MF, bool ALIGNED, bool SPLIT>
+__device__ __forceinline__ void tap_fwd_body(
     const unsigned short* __restrict__ x, const unsigned short* __restrict__ Wt,
     const float* __restrict__ bias, unsigned short* __restrict__ out,
-    TapGeom g) {
+    float* __restrict__ part, const TapGeom& g) {
   using T = Tile<R, S>;
   constexpr int TH = T::TH, TW = T::TW, PH = T::PH, PADL = T::PADL;
   constexpr int PWN = T::PWN, PWL = T::PWL, PBUF = T::PBUF, ES = T::ES;
@@ -291,10 +326,17 @@ __global__ __launch_bounds__(256) void tap_fwd_kernel(
   constexpr int FPR = TW / 16;        // fragments per tile row
   constexpr int NF = TH * FPR / 4;    // fragments per wave
   static_assert(NF == 4, "16 fragments per tile, four per wave");
-  constexpr int LDS_SHORTS = 2 * PBUF > KB * ES ? 2 * PBUF : KB * ES;
+  // SPLIT: the fp32 epilogue image takes EP row fragments at a time, as many
+  // as fit the patch buffers, so the split kernel needs no more LDS
+  constexpr int ESF = TH * TW + 4;    // its row stride in floats
+  constexpr int EPFIT = PBUF / (16 * ESF);
+  constexpr int EP = MF < EPFIT ? MF : EPFIT;
+  static_assert(EP >= 1, "one row fragment of the fp32 image fits");
+  constexpr int LDS_SHORTS =
+      SPLIT || 2 * PBUF > KB * ES ? 2 * PBUF : KB * ES;
 
-  // block -> (k tile, column block, row block, image), XCD-aware bijective
-  // swizzle as in conv_fwd_kernel
+  // block -> (k tile, [channel slice,] column block, row block, image),
+  // XCD-aware bijective swizzle as in conv_fwd_kernel
   const int nwg = gridDim.x;
   const int q8 = nwg >> 3, r8 = nwg & 7;
   const int xcd = blockIdx.x & 7, sub = blockIdx.x >> 3;
@@ -302,6 +344,17 @@ __global__ __launch_bounds__(256) void tap_fwd_kernel(
   if (bid >= nwg) bid = blockIdx.x;  // never taken: the mapping is bijective
   const int kt = bid % g.k_tiles;
   bid /= g.k_tiles;
+  // this block's chunks [ch_b, ch_e): all of them, or slice sc of g.sc, dealt
+  // evenly with the remainder to the earlier slices (g.sc <= chunks: >= 1)
+  const int chunks = g.Cp / CK;
+  int sc = 0, ch_b = 0, ch_e = chunks;
+  if constexpr (SPLIT) {
+    sc = bid % g.sc;
+    bid /= g.sc;
+    const int q = chunks / g.sc, rem = chunks % g.sc;
+    ch_b = sc * q + (sc < rem ? sc : rem);
+    ch_e = ch_b + q + (sc < rem ? 1 : 0);
+  }
   const int cb = bid % g.col_blocks;
   bid /= g.col_blocks;
   const int rb = bid % g.row_blocks;
@@ -456,15 +509,14 @@ __global__ __launch_bounds__(256) void tap_fwd_kernel(
     for (int nf = 0; nf < NF; ++nf) acc[mf][nf] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   s16x8 a_cur[MF], a_nxt[MF];
-  stage_load(0);
-  load_a(a_cur, 0, 0);
-  stage_commit(0, 0);
+  stage_load(ch_b * CK);
+  load_a(a_cur, 0, ch_b * CK);
+  stage_commit(0, ch_b * CK);
   __syncthreads();
 
-  const int chunks = g.Cp / CK;
-  for (int ch = 0; ch < chunks; ++ch) {
-    const int buf = ch & 1;
-    const bool more = ch + 1 < chunks;
+  for (int ch = ch_b; ch < ch_e; ++ch) {
+    const int buf = (ch - ch_b) & 1;
+    const bool more = ch + 1 < ch_e;
     if (more) stage_load((ch + 1) * CK);
     const short* pb = lds + buf * PBUF;
 #pragma unroll
@@ -489,6 +541,57 @@ __global__ __launch_bounds__(256) void tap_fwd_kernel(
     }
     if (more) stage_commit(buf ^ 1, (ch + 1) * CK);
     __syncthreads();
+  }
+
+  // ---- epilogue of a slice: the accumulators as they are, to part[sc] -------
+  // F image: [k][pixel] fp32 over the patch buffers, EP row fragments a pass,
+  // rows ESF floats apart (4 rows are 16 banks apart: the four 16-lane groups
+  // of a write do not collide). item = (k, 4-pixel segment).
+  if constexpr (SPLIT) {
+    float* F = (float*)lds;
+    constexpr int SEG4 = TH * TW / 4;
+    const int64_t OHW = (int64_t)g.OH * g.OW;
+    float* pn = part + ((int64_t)sc * g.N + n) * g.K * OHW;
+#pragma unroll
+    for (int m0 = 0; m0 < MF; m0 += EP) {
+      if (m0 > 0) __syncthreads();  // the reads of the pass before
+#pragma unroll
+      for (int e = 0; e < EP; ++e) {
+        const int mf = m0 + e < MF ? m0 + e : MF - 1;
+        if (m0 + e < MF) {
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const int k = e * 16 + ((lane >> 4) << 2) + reg;
+#pragma unroll
+            for (int nf = 0; nf < NF; ++nf) {
+              const int f = wid * NF + nf;
+              const int pix = (f / FPR) * TW + (f % FPR) * 16 + (lane & 15);
+              F[k * ESF + pix] = acc[mf][nf][reg];
+            }
+          }
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int it = 0; it < EP * 16 * SEG4 / 256; ++it) {
+        const int idx = it * 256 + tid;
+        const int seg = idx % SEG4, k = idx / SEG4;
+        const int kout = k0 + m0 * 16 + k;
+        const int oh = oh0 + seg / (TW / 4), ow = ow0 + (seg % (TW / 4)) * 4;
+        if (m0 * 16 + k >= KB || kout >= g.K || oh >= g.OH || ow >= g.OW)
+          continue;
+        const f32x4 v = *(const f32x4*)(F + k * ESF + seg * 4);
+        float* dst = pn + (int64_t)kout * OHW + (int64_t)oh * g.OW + ow;
+        if (g.vec_out) {  // OW % 4 == 0: the segment is whole
+          *(f32x4*)dst = v;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (ow + e < g.OW) dst[e] = v[e];
+        }
+      }
+    }
+    return;
   }
 
   // ---- epilogue --------------------------------------------------------------
@@ -534,6 +637,68 @@ __global__ __launch_bounds__(256) void tap_fwd_kernel(
           dst[e] = (unsigned short)(((unsigned)v[e >> 1] >> ((e & 1) * 16)) &
                                     0xffff);
     }
+  }
+}
+
+template <int R, int S, int MF, bool ALIGNED>
+__global__ __launch_bounds__(256) void tap_fwd_kernel(
+    const unsigned short* __restrict__ x, const unsigned short* __restrict__ Wt,
+    const float* __restrict__ bias, unsigned short* __restrict__ out,
+    TapGeom g) {
+  tap_fwd_body<R, S, MF, ALIGNED, false>(x, Wt, bias, out, nullptr, g);
+}
+
+// ---------------------------------------------------------------------------
+// Split channels (header: "Split channels")
+// ---------------------------------------------------------------------------
+
+// MF <= 4 and two blocks a CU: at most 76800 B of LDS, and the registers held
+// to 256 a lane, except for MF = 4 by elements, which then spilled 18 - 77
+// registers a lane
+template <int R, int S, int MF, bool ALIGNED>
+__global__ __launch_bounds__(256, (ALIGNED || MF < 4) ? 2 : 1)
+void tap_fwd_split_kernel(
+    const unsigned short* __restrict__ x, const unsigned short* __restrict__ Wt,
+    float* __restrict__ part, TapGeom g) {
+  tap_fwd_body<R, S, MF, ALIGNED, true>(x, Wt, nullptr, nullptr, part, g);
+}
+
+// out[i] = bf16(part[0][i] + part[1][i] + ... + part[sc-1][i] + bias[k(i)]),
+// summed in that order in fp32, i over the `total` = N*K*OH*OW elements.
+// VEC (OH*OW % 8 == 0, 16-byte aligned bases): a thread takes 8 elements of
+// one (image, channel) plane, two 16-byte loads a slice and one 16-byte store;
+// otherwise one element a thread.
+template <bool VEC>
+__global__ __launch_bounds__(256) void tap_split_reduce_kernel(
+    const float* __restrict__ part, const float* __restrict__ bias,
+    unsigned short* __restrict__ out, int sc, int K, int64_t OHW,
+    int64_t total) {
+  constexpr int E = VEC ? 8 : 1;
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * E;
+  if (i >= total) return;
+  const float b = bias ? bias[(i / OHW) % K] : 0.f;
+  if constexpr (VEC) {
+    f32x4 lo = *(const f32x4*)(part + i), hi = *(const f32x4*)(part + i + 4);
+    for (int s = 1; s < sc; ++s) {
+      const float* p = part + s * total + i;
+      const f32x4 l = *(const f32x4*)p, h = *(const f32x4*)(p + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        lo[e] += l[e];
+        hi[e] += h[e];
+      }
+    }
+    i32x4 o;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      o[j] = pack_bf16(lo[2 * j] + b, lo[2 * j + 1] + b);
+      o[j + 2] = pack_bf16(hi[2 * j] + b, hi[2 * j + 1] + b);
+    }
+    *(i32x4*)(out + i) = o;
+  } else {
+    float v = part[i];
+    for (int s = 1; s < sc; ++s) v += part[s * total + i];
+    out[i] = (unsigned short)(pack_bf16(v + b, 0.f) & 0xffff);
   }
 }
 
@@ -1369,6 +1534,7 @@ static TapGeom make_geom(int64_t N, int64_t C, int64_t K, int64_t H, int64_t W,
   g.col_blocks = (g.OW + ch.tw - 1) / ch.tw;
   g.k_tiles = (g.K + ch.mf * 16 - 1) / (ch.mf * 16);
   g.vec_out = g.OW % 8 == 0;
+  g.sc = 1;
   return g;
 }
 
@@ -1378,9 +1544,72 @@ std::string tap_kernel_name(int64_t C, int64_t K, int64_t H, int64_t W,
   return choose((int)K, (int)W, (int)R, (int)S, true).label;
 }
 
+// ---- split channels ---------------------------------------------------------
+
+using SplitKern = void (*)(const unsigned short*, const unsigned short*,
+                           float*, TapGeom);
+constexpr int SPLIT_MAX = 8;  // slices of a launch at most
+
+// MF of a split launch: the unsplit chooser's, but 4 where that is 7 (header)
+static int split_mf(int K) { return std::min(choose_mf(K), 4); }
+
+template <int R, int S>
+static TapChoice choose_split_rs(int mf, bool aligned, SplitKern& kern) {
+  using T = Tile<R, S>;
+  if (mf == 2)
+    kern = aligned ? tap_fwd_split_kernel<R, S, 2, true>
+                   : tap_fwd_split_kernel<R, S, 2, false>;
+  else
+    kern = aligned ? tap_fwd_split_kernel<R, S, 4, true>
+                   : tap_fwd_split_kernel<R, S, 4, false>;
+  return {nullptr, mf, T::TH, T::TW,
+          "tap_split<" + std::to_string(R) + "x" + std::to_string(S) + "," +
+              std::to_string(mf) + ">"};
+}
+
+static TapChoice choose_split(int mf, int W, int R, int S, bool base_aligned,
+                              SplitKern& kern) {
+  const bool aligned = base_aligned && W % 8 == 0;
+  if (R == 1 && S == 7) return choose_split_rs<1, 7>(mf, aligned, kern);
+  if (R == 7 && S == 1) return choose_split_rs<7, 1>(mf, aligned, kern);
+  return choose_split_rs<3, 3>(mf, aligned, kern);
+}
+
+// (MF, SC) of a problem on a device of `cus` compute units: the one place that
+// decides whether and how far the channels are split (rule: file header).
+// SC == 1: the unsplit kernel with the unsplit chooser's MF.
+std::pair<int, int> tap_split_choice(int64_t N, int64_t C, int64_t K,
+                                     int64_t H, int64_t W, int64_t R,
+                                     int64_t S, int64_t ph, int64_t pw,
+                                     int64_t cus) {
+  const TapChoice un = choose((int)K, (int)W, (int)R, (int)S, true);
+  const int64_t OH = H + 2 * ph - R + 1, OW = W + 2 * pw - S + 1;
+  const int64_t tiles =
+      N * ((OH + un.th - 1) / un.th) * ((OW + un.tw - 1) / un.tw);
+  auto k_tiles = [&](int mf) { return (K + mf * 16 - 1) / (mf * 16); };
+  if (k_tiles(un.mf) * tiles >= 2 * cus) return {un.mf, 1};
+  const int mf = split_mf((int)K);
+  const int64_t cap = std::min<int64_t>((C + CK - 1) / CK, SPLIT_MAX);
+  int64_t sc = 1;
+  while (sc < cap && k_tiles(mf) * tiles * sc < 2 * cus) ++sc;
+  if (sc == 1) return {un.mf, 1};
+  return {mf, (int)sc};
+}
+
+std::pair<std::string, int64_t> tap_split_kernel_name(
+    int64_t N, int64_t C, int64_t K, int64_t H, int64_t W, int64_t R,
+    int64_t S, int64_t ph, int64_t pw, int64_t cus) {
+  check_problem(N, C, K, H, W, R, S, ph, pw, "tap_split_kernel_name");
+  TORCH_CHECK(cus >= 1, "tap_split_kernel_name: cus must be positive");
+  const auto [mf, sc] = tap_split_choice(N, C, K, H, W, R, S, ph, pw, cus);
+  if (sc == 1) return {choose((int)K, (int)W, (int)R, (int)S, true).label, 1};
+  SplitKern kern;
+  return {choose_split(mf, (int)W, (int)R, (int)S, true, kern).label, sc};
+}
+
 torch::Tensor tap_fwd(torch::Tensor x, torch::Tensor w,
                       c10::optional<torch::Tensor> bias, int64_t ph, int64_t pw,
-                      bool transposed) {
+                      bool transposed, int64_t split) {
   TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.get_device() == w.get_device(),
               "tap_fwd: x and w must be on one GPU");
   TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && x.is_contiguous() &&
@@ -1395,8 +1624,24 @@ torch::Tensor tap_fwd(torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(x.size(1) == Cred, "tap_fwd: channel mismatch: x has ", x.size(1),
               ", the filter reduces over ", Cred);
   const bool base_aligned = ((uintptr_t)x.data_ptr() & 15) == 0;
+  // split: 0 the unsplit kernel, -1 the chooser's slices, n > 0 n slices
+  const int64_t chunks = (Cred + CK - 1) / CK;
+  TORCH_CHECK(split >= -1, "tap_fwd: split must be -1, 0 or a slice count");
+  TORCH_CHECK(split <= chunks, "tap_fwd: split = ", split, " slices, but C = ",
+              Cred, " has only ", chunks, " chunks of ", CK, " channels");
+  TORCH_CHECK(split <= SPLIT_MAX, "tap_fwd: split = ", split,
+              " slices, at most ", SPLIT_MAX, " are supported");
+  int sc = (int)split, smf = split_mf((int)Kout);
+  if (split < 0) {
+    const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    std::tie(smf, sc) = tap_split_choice(x.size(0), Cred, Kout, x.size(2),
+                                         x.size(3), R, S, ph, pw, cus);
+  }
+  SplitKern skern = nullptr;
   const TapChoice ch =
-      choose((int)Kout, (int)x.size(3), (int)R, (int)S, base_aligned);
+      sc > 1 ? choose_split(smf, (int)x.size(3), (int)R, (int)S, base_aligned,
+                            skern)
+             : choose((int)Kout, (int)x.size(3), (int)R, (int)S, base_aligned);
   TapGeom g = make_geom(x.size(0), Cred, Kout, x.size(2), x.size(3), R, S, ph,
                         pw, ch);
   const float* bptr = nullptr;
@@ -1413,17 +1658,40 @@ torch::Tensor tap_fwd(torch::Tensor x, torch::Tensor w,
   auto stream = at::cuda::getCurrentCUDAStream();
   const int64_t fblocks = ((int64_t)g.Kp * g.Cp + 255) / 256;
   const int64_t blocks =
-      (int64_t)g.k_tiles * g.row_blocks * g.col_blocks * g.N;
+      (int64_t)g.k_tiles * g.row_blocks * g.col_blocks * g.N * std::max(sc, 1);
   TORCH_CHECK(fblocks < (1LL << 31) && blocks < (1LL << 31),
               "tap_fwd: grid too large");
   hipLaunchKernelGGL(tap_filter_kernel, dim3((uint32_t)fblocks), dim3(256), 0,
                      stream.stream(), (const unsigned short*)w.data_ptr(),
                      (unsigned short*)Wt.data_ptr(), (int)Cw, g.K, g.C, g.Kp,
                      g.Cp, (int)(R * S), transposed ? 1 : 0);
-  hipLaunchKernelGGL(ch.kern, dim3((uint32_t)blocks), dim3(256), 0,
+  if (sc <= 1) {
+    hipLaunchKernelGGL(ch.kern, dim3((uint32_t)blocks), dim3(256), 0,
+                       stream.stream(), (const unsigned short*)x.data_ptr(),
+                       (const unsigned short*)Wt.data_ptr(), bptr,
+                       (unsigned short*)out.data_ptr(), g);
+    return out;
+  }
+  // split: partial sums of the slices, then their sum, the bias and rounding
+  const int64_t OHW = (int64_t)g.OH * g.OW, total = out.numel();
+  auto part = torch::empty({sc, g.N, g.K, g.OH, g.OW},
+                           x.options().dtype(torch::kFloat));
+  const bool part_al = ((uintptr_t)part.data_ptr() & 15) == 0;
+  const bool vec_red = OHW % 8 == 0 && part_al &&
+                       ((uintptr_t)out.data_ptr() & 15) == 0;
+  const int64_t rblocks = (total / (vec_red ? 8 : 1) + 255) / 256;
+  TORCH_CHECK(rblocks < (1LL << 31), "tap_fwd: grid too large");
+  g.sc = sc;
+  g.vec_out = g.OW % 4 == 0 && part_al;  // 16 bytes are four fp32 here
+  hipLaunchKernelGGL(skern, dim3((uint32_t)blocks), dim3(256), 0,
                      stream.stream(), (const unsigned short*)x.data_ptr(),
-                     (const unsigned short*)Wt.data_ptr(), bptr,
-                     (unsigned short*)out.data_ptr(), g);
+                     (const unsigned short*)Wt.data_ptr(),
+                     part.data_ptr<float>(), g);
+  hipLaunchKernelGGL(vec_red ? tap_split_reduce_kernel<true>
+                             : tap_split_reduce_kernel<false>,
+                     dim3((uint32_t)rblocks), dim3(256), 0, stream.stream(),
+                     (const float*)part.data_ptr<float>(), bptr,
+                     (unsigned short*)out.data_ptr(), sc, g.K, OHW, total);
   return out;
 }
 
@@ -1787,13 +2055,19 @@ torch::Tensor tap_bwd_weight_px(torch::Tensor go, torch::Tensor x, int64_t R,
 void register_conv_tap(pybind11::module_& m) {
   m.def("tap_fwd", &conv_tap::tap_fwd, pybind11::arg("x"), pybind11::arg("w"),
         pybind11::arg("bias"), pybind11::arg("ph"), pybind11::arg("pw"),
-        pybind11::arg("transposed") = false,
+        pybind11::arg("transposed") = false, pybind11::arg("split") = 0,
         "tap-shift direct stride-1 conv, 1x7 / 7x1 / 3x3 (bf16 NCHW); "
         "transposed: x is the output gradient, w the forward weight, the "
-        "result the data gradient");
+        "result the data gradient; split: 0 one block runs all channels, -1 "
+        "the channel chunks are dealt to as many slices as "
+        "tap_split_kernel_name says for this device, n > 0 to n slices");
   m.def("tap_kernel_name", &conv_tap::tap_kernel_name,
         "label of the kernel tap_fwd launches for (C, K, H, W, R, S, ph, pw); "
         "no tensor, no HIP call");
+  m.def("tap_split_kernel_name", &conv_tap::tap_split_kernel_name,
+        "(label, slices) of the launch of tap_fwd(split=-1) for (N, C, K, H, "
+        "W, R, S, ph, pw) on a device of `cus` compute units; slices == 1: "
+        "tap_kernel_name's kernel; no tensor, no HIP call");
   m.def("tap_bwd_weight", &conv_tap::tap_bwd_weight, pybind11::arg("go"),
         pybind11::arg("x"), pybind11::arg("R"), pybind11::arg("S"),
         pybind11::arg("ph"), pybind11::arg("pw"),

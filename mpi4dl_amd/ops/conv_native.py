@@ -48,7 +48,14 @@ Kernel families (csrc/):
   lie in memory, pixel-innermost (a 16-byte copy, no transpose in or out
   of LDS), on a 128 x 32 channel tile, and takes the column taps as
   register shifts of a 24-pixel window (PERF_NOTES, "Tap-shift weight
-  gradient, pixel-major").
+  gradient, pixel-major"). MPI4DL_TAPCONV_SPLIT=auto, also on top of the
+  first switch, runs the forward and data-grad legs as
+  ge.tap_fwd(split=-1): where the grid of a problem is under two blocks a
+  CU, tap_fwd_split_kernel deals the 32-channel chunks to up to 8 slices
+  of blocks that leave fp32 partial sums in a workspace, and
+  tap_split_reduce_kernel adds them in slice order, with the bias, and
+  rounds once; elsewhere it is the unsplit kernel (PERF_NOTES, "Tap-shift
+  conv, split channels").
 
 Per-shape, per-LEG policy (all crossovers measured on MI355X —
 profiles/PERF_NOTES.md): stride-2 1x1s, K<=64 1x1s, stems, wide
@@ -61,11 +68,13 @@ F.conv2d/MIOpen. MPI4DL_NATIVE_CONV=0 disables all native paths,
 
 The per-leg policy is written once, in ``conv_plan``: a pure function
 of the problem's integers and the MPI4DL_PW_BLASLT,
-MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1 and MPI4DL_TAPCONV_WGRAD=1|ring|px
-switches. ``ConvFn`` executes the plan and decides nothing itself; which
-kernel a native route then launches is the extension's choice
+MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1, MPI4DL_TAPCONV_WGRAD=1|ring|px
+and MPI4DL_TAPCONV_SPLIT=auto switches. ``ConvFn`` executes the plan and
+decides nothing itself; which kernel a native route then launches is the
+extension's choice
 (``conv_fwd_kernel_name``, ``pw_kernel_name``, ``pw_bwdw_kernel_name``,
-``wino_kernel_name``, ``tap_kernel_name``, ``tap_bwdw_kernel_name``,
+``wino_kernel_name``, ``tap_kernel_name``, ``tap_split_kernel_name``,
+``tap_bwdw_kernel_name``,
 ``tap_bwdw_ring_kernel_name``, ``tap_bwdw_px_kernel_name`` answer it for a
 plan's problems).
 """
@@ -131,6 +140,10 @@ def _tap_wgrad_mode():
     return v if v in ("ring", "px") else v == "1"
 
 
+def _tap_split_on():
+    return os.environ.get("MPI4DL_TAPCONV_SPLIT", "0") == "auto"
+
+
 def _tap_ok(H, W, R, S, sh, sw, ph, pw):
     """What conv_tap.hip serves: 1x7, 7x1 or 3x3, stride 1, pads in
     [0, R-1] x [0, S-1], at least one output pixel (dilation 1 and groups
@@ -165,6 +178,11 @@ class Leg(NamedTuple):
                              gradient); problem = tap_kernel_name's
                              (C, K, H, W, R, S, ph, pw), C and K as for
                              wino_fwd
+      tap_fwd_split          ge.tap_fwd(split=-1) (for gx: transposed, on the
+                             output gradient); problem =
+                             tap_split_kernel_name's (N, C, K, H, W, R, S,
+                             ph, pw) without the CU count, C and K as for
+                             wino_fwd
       tap_bwd_weight         ge.tap_bwd_weight; problem =
                              tap_bwdw_kernel_name's (N, C, K, H, W, R, S,
                              ph, pw), the forward convolution's
@@ -185,14 +203,15 @@ class ConvPlan(NamedTuple):
 
 
 def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
-              winograd=None, tap=None, tap_wgrad=None):
+              winograd=None, tap=None, tap_wgrad=None, tap_split=None):
     """The route of each leg of the convolution x[N,C,H,W] * w[K,C,R,S]
     and the problem that route hands to its binding. ``blaslt`` defaults
     to the MPI4DL_PW_BLASLT switch, ``winograd`` to
     MPI4DL_WINOGRAD == "fused", ``tap`` to MPI4DL_TAPCONV == "1" and
     ``tap_wgrad`` (looked at only where ``tap`` routes the problem; True,
-    False, "ring" or "px") to MPI4DL_TAPCONV_WGRAD == "1", "ring" or "px";
-    nothing else is read."""
+    False, "ring" or "px") to MPI4DL_TAPCONV_WGRAD == "1", "ring" or "px"
+    and ``tap_split`` (looked at only where ``tap`` routes the problem) to
+    MPI4DL_TAPCONV_SPLIT == "auto"; nothing else is read."""
     if blaslt is None:
         blaslt = _blaslt_on()
     if winograd is None:
@@ -251,10 +270,17 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
         if tap_wgrad not in (True, False, "ring", "px"):
             raise ValueError(f"tap_wgrad must be a bool, 'ring' or 'px', "
                              f"got {tap_wgrad!r}")
+        if tap_split is None:
+            tap_split = _tap_split_on()
         tapw = (N, C, K, H, W, R, S, ph, pw)
+        tapx = (K, C, OH, OW, R, S, R - 1 - ph, S - 1 - pw)
         return ConvPlan(
-            Leg("tap_fwd", (C, K, H, W, R, S, ph, pw)),
-            Leg("tap_fwd", (K, C, OH, OW, R, S, R - 1 - ph, S - 1 - pw)),
+            # the third switch lets the extension split the channels of
+            # both legs where their grids under-fill the device
+            (Leg("tap_fwd_split", tapw) if tap_split
+             else Leg("tap_fwd", tapw[1:])),
+            (Leg("tap_fwd_split", (N,) + tapx) if tap_split
+             else Leg("tap_fwd", tapx)),
             (Leg("tap_bwd_weight_ring", tapw) if tap_wgrad == "ring"
              else Leg("tap_bwd_weight_px", tapw) if tap_wgrad == "px"
              else Leg("tap_bwd_weight", tapw) if tap_wgrad
@@ -279,8 +305,9 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
 class ConvFn(torch.autograd.Function):
     """Executes ``conv_plan``. The plan is made once, in forward, and
     kept on ctx: backward reads none of MPI4DL_PW_BLASLT,
-    MPI4DL_WINOGRAD, MPI4DL_TAPCONV and MPI4DL_TAPCONV_WGRAD again, so a
-    change of a variable between a forward and its backward is ignored.
+    MPI4DL_WINOGRAD, MPI4DL_TAPCONV, MPI4DL_TAPCONV_WGRAD and
+    MPI4DL_TAPCONV_SPLIT again, so a change of a variable between a forward
+    and its backward is ignored.
 
     Weight gradient: the routes that run our own kernels (pw_bwdw,
     pw_bwdw_sub, conv_bwd_weight, tap_bwd_weight, tap_bwd_weight_ring,
@@ -307,6 +334,8 @@ class ConvFn(torch.autograd.Function):
             y = ge.wino_fwd(xb, wb, bias, ph, pw)
         elif plan.y.route == "tap_fwd":
             y = ge.tap_fwd(xb, wb, bias, ph, pw)
+        elif plan.y.route == "tap_fwd_split":
+            y = ge.tap_fwd(xb, wb, bias, ph, pw, split=-1)
         else:
             y = ge.conv_fwd(xb, wb, bias, sh, sw, ph, pw)
         ctx.save_for_backward(xb, wb)
@@ -375,6 +404,9 @@ class ConvFn(torch.autograd.Function):
         elif gx_route == "tap_fwd":
             # the filter pre-pass reads wb transposed and rotated itself
             gx = ge.tap_fwd(go, wb, None, R - 1 - ph, S - 1 - pw, True)
+        elif gx_route == "tap_fwd_split":
+            gx = ge.tap_fwd(go, wb, None, R - 1 - ph, S - 1 - pw, True,
+                            split=-1)
         else:
             # conv_fwd on go, or on go zero-stuffed to the plan's extents
             _, _, hs, ws, _, _, _, _, tph, tpw = ctx.plan.gx.problem
