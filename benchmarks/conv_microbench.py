@@ -170,6 +170,85 @@ def tap_ab(args):
                   flush=True)
 
 
+# (C = K, H = W, R, S) at stride (min(R, 2), min(S, 2)), "same" padding:
+# AmoebaNet's reduction-cell legs per plane, then the head of a ResNet stage
+TAP_STRIDED_SHAPES = (
+    [(c, hw, r, s) for c, hw in ((104, 256), (208, 128), (416, 64))
+     for r, s in ((1, 7), (7, 1))]
+    + [(c, hw, 3, 3) for c, hw in WINO_SHAPES[:3]]
+)
+
+
+def tap_strided_ab(args):
+    """Strided 1x7 / 7x1 / 3x3, forward and data-grad legs: the strided
+    tap-shift kernels (ge.tap_fwd_strided, ge.tap_bwd_data_strided, filter
+    pre-pass included), the current native routes (ge.conv_fwd; for the
+    data-grad conv_fwd_zs as ConvFn runs it: zero fill, scatter, weight
+    transpose and flip, then the stride-1 kernel) and MIOpen. Same protocol as
+    --tap: all variants warmed up, alternating rounds, median; ratios are
+    MIOpen's time over the variant's."""
+    import torch.nn.functional as F
+
+    from mpi4dl_amd.ops import backend
+    from mpi4dl_amd.ops.conv_native import conv_plan
+
+    ge = backend.ext()
+    names = ("tap", "native", "miopen")
+    print(f"{'shape':<34}{'leg':<5}" + "".join(f"{n:>11}" for n in names)
+          + "   tap/native vs miopen  winner")
+    N = args.batch
+    for C, hw, R, S in TAP_STRIDED_SHAPES:
+        sh, sw, ph, pw = min(R, 2), min(S, 2), R // 2, S // 2
+        plan = conv_plan(N, C, C, hw, hw, R, S, sh, sw, ph, pw, tap=False)
+        _, _, hs, ws, _, _, _, _, tph, tpw = plan.gx.problem
+        x = torch.randn(N, C, hw, hw, device="cuda", dtype=torch.bfloat16)
+        wb = (torch.randn(C, C, R, S, device="cuda") * 0.05).to(torch.bfloat16)
+        go = torch.randn_like(F.conv2d(x, wb, stride=(sh, sw), padding=(ph, pw)))
+
+        def zero_stuffed():
+            src = torch.zeros(N, C, hs, ws, device=go.device, dtype=go.dtype)
+            src[:, :, ::sh, ::sw] = go
+            wt = wb.transpose(0, 1).flip(2, 3).contiguous()
+            return ge.conv_fwd(src, wt, None, 1, 1, tph, tpw)
+
+        legs = {
+            "fwd": {
+                "tap": lambda: ge.tap_fwd_strided(x, wb, None, sh, sw, ph, pw),
+                "native": lambda: ge.conv_fwd(x, wb, None, sh, sw, ph, pw),
+                "miopen": lambda: F.conv2d(x, wb, stride=(sh, sw),
+                                           padding=(ph, pw)),
+            },
+            "gx": {
+                "tap": lambda: ge.tap_bwd_data_strided(go, wb, hw, hw, sh, sw,
+                                                       ph, pw),
+                "native": zero_stuffed,
+                "miopen": lambda: torch.nn.grad.conv2d_input(
+                    x.shape, wb, go, stride=(sh, sw), padding=(ph, pw)),
+            },
+        }
+        for leg, fns in legs.items():
+            for fn in fns.values():
+                timeit(fn, 2, warmup=3)
+            rounds = {n: [] for n in names}
+            for _ in range(5):
+                for n in names:
+                    rounds[n].append(
+                        timeit(fns[n], max(args.iters // 5, 2), warmup=0))
+            t = {n: sorted(v)[len(v) // 2] for n, v in rounds.items()}
+            ref = fns["miopen"]().float()
+            rel = ((fns["tap"]().float() - ref).abs().max().item()
+                   / max(ref.abs().max().item(), 1e-3))
+            assert torch.equal(fns["tap"](), fns["tap"]())
+            tag = f"C{C}->K{C} {hw}x{hw} k{R}x{S} s{sh}{sw} N{N}"
+            kname = ge.tap_strided_kernel_name(C, C, hw, hw, R, S, sh, sw, ph,
+                                               pw, leg == "gx")
+            print(f"{tag:<34}{leg:<5}"
+                  + "".join(f"{t[n]:9.3f}ms" for n in names) + "   "
+                  + " ".join(f"{t['miopen'] / t[n]:5.2f}x" for n in names[:2])
+                  + f"  {min(t, key=t.get):<7}[{kname}]  tap relerr {rel:.3g}",
+                  flush=True)
+
+
 def tap_bwdw_ab(args):
     """The shapes of --tap, weight-gradient leg only: the tap-shift kernel
     (ge.tap_bwd_weight), its rolling-window variant (ge.tap_bwd_weight_ring),
@@ -400,6 +479,10 @@ def main():
                     help="A/B the tap-shift kernel and the direct kernel vs "
                          "MIOpen on the stride-1 1x7, 7x1 and 3x3 shapes, "
                          "forward and data-grad")
+    ap.add_argument("--tap-strided", action="store_true",
+                    help="A/B the strided tap-shift kernels vs the native "
+                         "routes and MIOpen on the strided 1x7 / 7x1 / 3x3 "
+                         "shapes, forward and data-grad")
     ap.add_argument("--tap-bwdw", action="store_true",
                     help="A/B the tap-shift weight-gradient kernels (rolling "
                          "window and first) and conv_bwd_weight vs MIOpen on "
@@ -418,6 +501,8 @@ def main():
         return winograd_ab(args)
     if args.tap:
         return tap_ab(args)
+    if args.tap_strided:
+        return tap_strided_ab(args)
     if args.tap_bwdw:
         return tap_bwdw_ab(args)
     if args.pw:

@@ -76,6 +76,67 @@
 //   allowed if none does. If that SC is 1 the launch is the unsplit kernel
 //   with its own MF. A forced slice count uses the same MF.
 //
+// Strided: tap_strided_fwd_kernel<R, S, MF, ALIGNED> and
+// tap_strided_bwd_data_kernel<R, S, MF, ALIGNED>, for 1x7 at stride (1, 2),
+// 7x1 at (2, 1) and 3x3 at (2, 2) (sh = 2 where R > 1, sw = 2 where S > 1),
+// the same pads, Wt and pre-pass. Opt-in: tap_fwd_strided,
+// tap_bwd_data_strided.
+//
+// * Forward. The scheme above (32-channel chunks, double-buffered patch, k over
+//   the channels of one tap, weights one tap ahead in registers, bf16 epilogue
+//   over the patch) on a patch of ((TH-1)*sh + R) x ((TW-1)*sw + S) pixels. A
+//   B fragment is 16 consecutive output columns: input columns sw apart. On
+//   the [row][col] image that read steps 160 bytes a lane, 40 banks: lane i
+//   starts on bank 40*i mod 64 = 0,40,16,56,32,8,48,24 and again 0: lanes i
+//   and i + 8 share a 4-bank span, a 2-way conflict on every tap. So the patch
+//   is staged phase-split: patch column lc lies in column plane lc % sw at
+//   index lc / sw, patch row lr in row plane lr % sh at lr / sh, every plane
+//   [row][col][32 ch] at 80 bytes a pixel. Output column j of tap s is patch
+//   column j*sw + cc, cc = PADL - pw + s: plane cc % sw, index j + cc / sw,
+//   the same plane for all 16 lanes and one pixel a lane. Tap (r, s) of
+//   fragment (row, col0) is again one ds_read_b128, at
+//   plane(r % sh, cc % sw) + ((row + r/sh) * PWP + col0 + (lane & 15) + cc/sw)
+//   * 80 B + (lane >> 4) * 16 B: lane i starts on bank 20*i mod 64 =
+//   0,20,40,60,16,36,56,12,32,52,8,28,48,4,24,44, sixteen disjoint 4-bank
+//   spans at every constant offset, as at stride 1.
+//   The de-interleave is free on the ALIGNED path: each of the eight
+//   ds_write_b128 after the v_perm transpose carries one pixel, and pixel p of
+//   a group goes to plane p % sw, p / sw pixels on. The patch has more than
+//   256 (row, 8 pixels, 8 channels) items: two a thread. By elements wave cg
+//   stages channel group cg, a lane one pixel per ds_write_b128.
+// * Tiles and LDS (80 B a pixel, two buffers; PWL = columns in LDS):
+//     1x7  4 x 64   patch  4 x 133, PWL 144: 2 planes of  4 x 72   92160 B
+//     7x1  8 x 32   patch 21 x  32, PWL  32: 2 planes of 11 x 32  112640 B
+//     3x3  4 x 32   patch  9 x  65, PWL  80: 4 planes of  5 x 40  128000 B
+//   3x3 at the stride-1 tile, 8 x 32, is 17 x 80 pixels, 2 x 108800 B, over
+//   the 160 KB; 8 x 16 is 17 x 48, 130560 B and 6.4 staged pixels per output
+//   pixel where 4 x 32 has 5.6. So 3x3 runs 8 fragments a tile, two a wave,
+//   and a weight fragment feeds 2 MFMAs, not 4. MF is the stride-1 chooser's.
+// * Data gradient, by phase decomposition:
+//     gx[h][w] = sum_k sum_(r,s) go[k][(h+ph-r)/sh][(w+pw-s)/sw] * w[k][c][r][s]
+//   over the taps with r = (h + ph) mod sh and s = (w + pw) mod sw. The taps
+//   of class (ra, rb) = (r % sh, s % sw) serve exactly the gx pixels of phase
+//   a = (ra - ph) mod sh, b = (rb - pw) mod sw: 4 + 3 taps for the 1-D
+//   filters, 4 + 2 + 2 + 1 for 3x3, and each class is a stride-1 tap-shift
+//   convolution of go. Tap r = ra + sh*m of the class reads go row
+//   i + (a + ph - ra)/sh - m for the gx row i*sh + a.
+//   All phases in one block (the baseline; none spilled, so the
+//   phase-per-block grid, which restages go sh*sw times, was not built): a
+//   block owns TH x TW phase cells (go pixels), TH*sh x TW*sw pixels of gx,
+//   with the tiles of the forward. It stages the go patch once per 32-channel
+//   chunk of K in the plain stride-1 layout, (TH + (R-1)/sh + sh-1) rows x
+//   (TW + (S-1)/sw + sw-1) columns (4 x 68, 12 x 32, 6 x 34: at most 2 x
+//   30720 B), and walks all R*S taps class by class against it, each class
+//   into its own accumulators: sh*sw * MF * NF fragments, so MF is at most 4
+//   for 3x3 (128 registers; 1x7 and 7x1 at MF = 7: 224). Wt is the transposed
+//   pre-pass as it is; a class only selects the tap indices.
+//   Epilogue: the classes interleaved in the [c][pixel] image of the gx tile
+//   (116480 B at MF = 7, over the patch), pixel (row*sh + a, col*sw + b), then
+//   16-byte row stores where W % 8 == 0, guarded element stores otherwise.
+//   Every pixel of [0, H) x [0, W) is written: go outside its extents is
+//   staged as zeros, which makes borders, and the rows and columns that no
+//   filter position reaches, exact zeros. No atomics, fixed summation order.
+//
 // Weight gradient: tap_bwdw_kernel<R, S, XAL, GAL>
 //
 //   gw[k][c][r][s] += sum_{n,oh,ow} go[n][k][oh][ow] * x[n][c][oh-ph+r][ow-pw+s]
@@ -1446,6 +1507,487 @@ __global__ __launch_bounds__(256) void tap_bwdw_px_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Strided (header: "Strided")
+// ---------------------------------------------------------------------------
+
+// Geometry of a strided filter shape, shared by the kernels and the host: 1x7
+// runs at stride (1, 2), 7x1 at (2, 1), 3x3 at (2, 2). The tile is TH x TW
+// output pixels in the forward and TH x TW phase cells (go pixels) in the
+// data gradient.
+template <int R, int S>
+struct Strided {
+  static constexpr int SH = R > 1 ? 2 : 1, SW = S > 1 ? 2 : 1;
+  static constexpr int TH = R == 7 ? 8 : 4;
+  static constexpr int TW = S == 7 ? 64 : 32;
+  static constexpr int PADL = S > 1 ? 8 : 0;  // patch columns left of the tile
+  // forward: the input patch
+  static constexpr int FPH = (TH - 1) * SH + R;
+  static constexpr int FPWN = (TW - 1) * SW + S;
+  static constexpr int FPWL = (PADL + FPWN + 7) / 8 * 8;
+  // data gradient: the go patch; a class walks MR + 1 row and MS + 1 column
+  // taps at most, and two classes lie at most one go pixel apart
+  static constexpr int MR = (R - 1) / SH, MS = (S - 1) / SW;
+  static constexpr int BPH = TH + MR + SH - 1;
+  static constexpr int BPWN = TW + MS + SW - 1;
+  static constexpr int BPWL = (PADL + BPWN + 7) / 8 * 8;
+};
+
+// One 32-channel chunk of a PH x PWL patch of an NCHW image on its way into
+// LDS: channel-innermost, PSTR shorts a pixel, in SH x SW phase planes. Patch
+// (row pr, column lc) lies in plane (pr % SH, lc % SW) at (pr / SH, lc / SW).
+// Loads, v_perm transpose and masks as in tap_fwd_body, which keeps its own
+// copy. ALIGNED: an item is (patch row, 8-pixel group, 8-channel group), its
+// eight ds_write_b128 go to alternating column planes. Otherwise wave cg
+// stages channel group cg, an item is one pixel of the PWN needed columns.
+template <int PH, int PWL, int PWN, int SH, int SW, bool ALIGNED>
+struct PhasePatch {
+  static constexpr int PHP = (PH + SH - 1) / SH, PWP = PWL / SW;
+  static constexpr int PLANE = PHP * PWP * PSTR;   // shorts per plane
+  static constexpr int PBUF = SH * SW * PLANE;     // shorts per buffer
+  static constexpr int G = PWL / 8;
+  static constexpr int TASKS = PH * G * 4, PIX = PH * PWN;
+  static constexpr int NT = ALIGNED ? (TASKS + 255) / 256 : (PIX + 63) / 64;
+  static_assert(PWL % 8 == 0 && 8 % SW == 0, "8-pixel groups split evenly");
+  int soff[NT];  // offset in the channel plane; -1: outside the image, zeros
+  int sdst[NT];  // LDS short index of the first write; -1: no item
+  i32x4 rawv[ALIGNED ? NT : 1][8];
+  unsigned raws[ALIGNED ? 1 : NT][8];
+
+  static __device__ __forceinline__ int dst(int pr, int lc) {
+    return ((pr % SH) * SW + lc % SW) * PLANE +
+           ((pr / SH) * PWP + lc / SW) * PSTR;
+  }
+  static __device__ __forceinline__ int group(int tid) {
+    return ALIGNED ? tid & 3 : tid >> 6;
+  }
+
+  // (row0, col0): image coordinates of patch row 0 and patch column 0
+  // (ALIGNED: col0 % 8 == 0 and Wi % 8 == 0, a group is wholly in or out);
+  // by elements the columns [lc0, lc0 + PWN) are staged
+  __device__ __forceinline__ void locate(int tid, int row0, int col0, int lc0,
+                                         int Hi, int Wi) {
+#pragma unroll
+    for (int it = 0; it < NT; ++it) {
+      int pr, lc;
+      bool live;
+      if constexpr (ALIGNED) {
+        const int u = (it * 256 + tid) >> 2;
+        lc = (u % G) * 8;
+        pr = u / G;
+        live = it * 256 + tid < TASKS;
+      } else {
+        const int v = it * 64 + (tid & 63);
+        lc = lc0 + v % PWN;
+        pr = v / PWN;
+        live = v < PIX;
+      }
+      const int ih = row0 + pr, iw = col0 + lc;
+      const bool ok = live && ih >= 0 && ih < Hi && iw >= 0 && iw < Wi;
+      soff[it] = ok ? ih * Wi + iw : -1;
+      sdst[it] = live ? dst(pr, lc) + group(tid) * 8 : -1;
+    }
+  }
+
+  // issue the loads of channels c0 .. c0 + 32 (clamped below Cmax and into
+  // the plane: always inside the image); nothing reads them before `commit`
+  __device__ __forceinline__ void load(const unsigned short* img, int64_t HW,
+                                       int c0, int Cmax, int tid) {
+#pragma unroll
+    for (int it = 0; it < NT; ++it) {
+      if (sdst[it] < 0) continue;
+      const int off = soff[it] < 0 ? 0 : soff[it];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = c0 + group(tid) * 8 + e;
+        const unsigned short* p = img + (int64_t)(c < Cmax ? c : Cmax - 1) * HW + off;
+        if constexpr (ALIGNED)
+          rawv[it][e] = *(const i32x4*)p;
+        else
+          raws[it][e] = *p;
+      }
+    }
+  }
+
+  // pads, borders and the channel tail become zeros here
+  __device__ __forceinline__ void commit(short* pb, int c0, int Cmax, int tid) {
+#pragma unroll
+    for (int it = 0; it < NT; ++it) {
+      if (sdst[it] < 0) continue;
+      const unsigned sm = soff[it] < 0 ? 0u : ~0u;
+      unsigned cm[4];  // dword j holds channels 2j (low) and 2j + 1
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = c0 + group(tid) * 8 + 2 * j;
+        cm[j] = sm & ((c < Cmax ? 0xffffu : 0u) | (c + 1 < Cmax ? 0xffff0000u : 0u));
+      }
+      if constexpr (ALIGNED) {
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+          // 8x8 transpose of 16-bit values: pixel p of channels 2j and 2j+1
+          const unsigned sel = (p & 1) ? 0x07060302u : 0x05040100u;
+          i32x4 o;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            o[j] = (int)(__builtin_amdgcn_perm((unsigned)rawv[it][2 * j + 1][p >> 1],
+                                               (unsigned)rawv[it][2 * j][p >> 1],
+                                               sel) & cm[j]);
+          // the group starts on a multiple of 8 columns: pixel p is in column
+          // plane p % SW, p / SW pixels on
+          *(i32x4*)(pb + sdst[it] + (p % SW) * PLANE + (p / SW) * PSTR) = o;
+        }
+      } else {
+        i32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o[j] = (int)((raws[it][2 * j] | (raws[it][2 * j + 1] << 16)) & cm[j]);
+        *(i32x4*)(pb + sdst[it]) = o;
+      }
+    }
+  }
+};
+
+// block -> (k tile, column block, row block, image): the XCD-aware bijective
+// swizzle of tap_fwd_body
+__device__ __forceinline__ void strided_block(const TapGeom& g, int& kt, int& cb,
+                                              int& rb, int& n) {
+  const int nwg = gridDim.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  const int xcd = blockIdx.x & 7, sub = blockIdx.x >> 3;
+  int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + sub;
+  if (bid >= nwg) bid = blockIdx.x;  // never taken: the mapping is bijective
+  kt = bid % g.k_tiles;
+  bid /= g.k_tiles;
+  cb = bid % g.col_blocks;
+  bid /= g.col_blocks;
+  rb = bid % g.row_blocks;
+  n = bid / g.row_blocks;
+}
+
+// The [k][pixel] bf16 image in LDS (rows ES shorts apart, EH x EW pixels) to
+// out[n][k0 + k][oh0 ..][ow0 ..]: 16-byte row stores where g.vec_out, guarded
+// element stores otherwise. item = (k, 8-pixel segment).
+template <int KB, int EH, int EW, int ES>
+__device__ __forceinline__ void strided_store(const unsigned short* E,
+                                              unsigned short* __restrict__ out,
+                                              const TapGeom& g, int n, int k0,
+                                              int oh0, int ow0, int tid) {
+  constexpr int SEGS = EH * EW / 8;
+  static_assert(KB * SEGS % 256 == 0, "whole passes");
+  const int64_t OHW = (int64_t)g.OH * g.OW;
+#pragma unroll 4
+  for (int it = 0; it < KB * SEGS / 256; ++it) {
+    const int idx = it * 256 + tid;
+    const int seg = idx % SEGS, k = idx / SEGS;
+    const int kout = k0 + k;
+    const int oh = oh0 + seg / (EW / 8), ow = ow0 + (seg % (EW / 8)) * 8;
+    if (kout >= g.K || oh >= g.OH || ow >= g.OW) continue;
+    const i32x4 v = *(const i32x4*)(E + k * ES + seg * 8);
+    unsigned short* dst =
+        out + ((int64_t)n * g.K + kout) * OHW + (int64_t)oh * g.OW + ow;
+    if (g.vec_out) {  // OW % 8 == 0: the segment is whole
+      *(i32x4*)dst = v;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (ow + e < g.OW)
+          dst[e] = (unsigned short)(((unsigned)v[e >> 1] >> ((e & 1) * 16)) &
+                                    0xffff);
+    }
+  }
+}
+
+template <int R, int S, int MF, bool ALIGNED>
+__global__ __launch_bounds__(256) void tap_strided_fwd_kernel(
+    const unsigned short* __restrict__ x, const unsigned short* __restrict__ Wt,
+    const float* __restrict__ bias, unsigned short* __restrict__ out,
+    TapGeom g) {
+  using T = Strided<R, S>;
+  using P = PhasePatch<T::FPH, T::FPWL, T::FPWN, T::SH, T::SW, ALIGNED>;
+  constexpr int SH = T::SH, SW = T::SW, TH = T::TH, TW = T::TW;
+  constexpr int PADL = T::PADL, PBUF = P::PBUF, RS = R * S;
+  constexpr int KB = MF * 16;
+  constexpr int FPR = TW / 16;        // fragments per tile row
+  constexpr int NF = TH * FPR / 4;    // fragments per wave
+  constexpr int ES = TH * TW + 8;     // epilogue row stride
+  constexpr int LDS_SHORTS = 2 * PBUF > KB * ES ? 2 * PBUF : KB * ES;
+  static_assert(LDS_SHORTS * 2 <= 160 * 1024, "LDS of one CU");
+
+  int kt, cb, rb, n;
+  strided_block(g, kt, cb, rb, n);
+  const int k0 = kt * KB;
+  const int oh0 = rb * TH, ow0 = cb * TW;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+
+  // patch double buffer; the epilogue's [k][pixel] image overlays it
+  __shared__ __attribute__((aligned(16))) short lds[LDS_SHORTS];
+
+  const int64_t HW = (int64_t)g.H * g.W;
+  const unsigned short* xn = x + (int64_t)n * g.C * HW;
+  // patch row pr is input row oh0*SH - ph + pr, patch column lc is input
+  // column ow0*SW - PADL + lc
+  P st;
+  st.locate(tid, oh0 * SH - g.ph, ow0 * SW - PADL, PADL - g.pw, g.H, g.W);
+
+  // weight fragments: as in tap_fwd_body
+  const int64_t wplane = (int64_t)g.Kp * g.Cp;
+  int64_t wrow[MF];
+#pragma unroll
+  for (int mf = 0; mf < MF; ++mf) {
+    const int row = k0 + mf * 16 + (lane & 15);
+    wrow[mf] = (int64_t)(row < g.Kp ? row : g.Kp - 1) * g.Cp + ((lane >> 4) << 3);
+  }
+  auto load_a = [&](s16x8 (&a)[MF], int t, int c0) {
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf)
+      a[mf] = *(const s16x8*)(Wt + t * wplane + wrow[mf] + c0);
+  };
+
+  // B fragment nf of this wave: tile row frow, columns col0 .. col0 + 15: the
+  // input pixels (frow*SH + r, (col0 + j)*SW + PADL - pw + s) of the patch,
+  // which for one tap lie in one plane, one pixel apart
+  int boff[NF];
+#pragma unroll
+  for (int nf = 0; nf < NF; ++nf) {
+    const int f = wid * NF + nf;
+    const int frow = f / FPR, col0 = (f % FPR) * 16;
+    boff[nf] = (frow * P::PWP + col0 + (lane & 15)) * PSTR + ((lane >> 4) << 3);
+  }
+
+  f32x4 acc[MF][NF];
+#pragma unroll
+  for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf) acc[mf][nf] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int chunks = g.Cp / CK;
+  s16x8 a_cur[MF], a_nxt[MF];
+  st.load(xn, HW, 0, g.C, tid);
+  load_a(a_cur, 0, 0);
+  st.commit(lds, 0, g.C, tid);
+  __syncthreads();
+
+  for (int ch = 0; ch < chunks; ++ch) {
+    const bool more = ch + 1 < chunks;
+    if (more) st.load(xn, HW, (ch + 1) * CK, g.C, tid);
+    const short* pb = lds + (ch & 1) * PBUF;
+#pragma unroll
+    for (int t = 0; t < RS; ++t) {
+      if (t + 1 < RS)
+        load_a(a_nxt, t + 1, ch * CK);
+      else if (more)
+        load_a(a_nxt, 0, (ch + 1) * CK);
+      const int toff = P::dst(t / S, PADL - g.pw + t % S);  // uniform
+      s16x8 bfrag[NF];
+#pragma unroll
+      for (int nf = 0; nf < NF; ++nf)
+        bfrag[nf] = *(const s16x8*)(pb + boff[nf] + toff);
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+        for (int nf = 0; nf < NF; ++nf)
+          acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a_cur[mf], bfrag[nf], acc[mf][nf], 0, 0, 0);
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf) a_cur[mf] = a_nxt[mf];
+    }
+    if (more) st.commit(lds + ((ch & 1) ^ 1) * PBUF, (ch + 1) * CK, g.C, tid);
+    __syncthreads();
+  }
+
+  // epilogue: bias, round to bf16, [k][pixel] image, row stores. D layout of
+  // the MFMA: row (lane >> 4)*4 + reg, column lane & 15.
+  unsigned short* E = (unsigned short*)lds;
+#pragma unroll
+  for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int k = mf * 16 + ((lane >> 4) << 2) + reg;
+      const int kout = k0 + k;
+      const float b = bias ? bias[kout < g.K ? kout : g.K - 1] : 0.f;
+#pragma unroll
+      for (int nf = 0; nf < NF; ++nf) {
+        const int f = wid * NF + nf;
+        const int pix = (f / FPR) * TW + (f % FPR) * 16 + (lane & 15);
+        E[k * ES + pix] =
+            (unsigned short)(pack_bf16(acc[mf][nf][reg] + b, 0.f) & 0xffff);
+      }
+    }
+  __syncthreads();
+  strided_store<KB, TH, TW, ES>(E, out, g, n, k0, oh0, ow0, tid);
+}
+
+// Data gradient by phase decomposition (header: "Strided"). TapGeom holds the
+// launch: C the channels of go (the reduction), H x W the extents of go, K the
+// channels of gx, OH x OW the extents of gx, ph and pw the forward's pads.
+template <int R, int S, int MF, bool ALIGNED>
+__global__ __launch_bounds__(256) void tap_strided_bwd_data_kernel(
+    const unsigned short* __restrict__ go, const unsigned short* __restrict__ Wt,
+    unsigned short* __restrict__ gx, TapGeom g) {
+  using T = Strided<R, S>;
+  using P = PhasePatch<T::BPH, T::BPWL, T::BPWN, 1, 1, ALIGNED>;
+  constexpr int SH = T::SH, SW = T::SW, TH = T::TH, TW = T::TW;
+  constexpr int PADL = T::PADL, PWL = T::BPWL, PBUF = P::PBUF;
+  constexpr int MR = T::MR, MS = T::MS;
+  constexpr int KB = MF * 16;
+  constexpr int FPR = TW / 16;
+  constexpr int NF = TH * FPR / 4;
+  constexpr int EH = TH * SH, EW = TW * SW;  // the tile in gx
+  constexpr int ES = EH * EW + 8;
+  constexpr int LDS_SHORTS = 2 * PBUF > KB * ES ? 2 * PBUF : KB * ES;
+  static_assert(LDS_SHORTS * 2 <= 160 * 1024, "LDS of one CU");
+
+  int kt, cb, rb, n;
+  strided_block(g, kt, cb, rb, n);
+  const int k0 = kt * KB;
+  const int i0 = rb * TH, j0 = cb * TW;  // first phase cell of the tile
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+
+  __shared__ __attribute__((aligned(16))) short lds[LDS_SHORTS];
+
+  const int64_t HW = (int64_t)g.H * g.W;
+  const unsigned short* gn = go + (int64_t)n * g.C * HW;
+  // Tap class (ra, rb) = (r % SH, s % SW) serves the gx pixels of phase
+  // a = (ra - ph) mod SH, b = (rb - pw) mod SW; its tap r = ra + SH*m reads go
+  // row i + (a + ph - ra)/SH - m for cell row i, and (a + ph - ra)/SH is qh or
+  // qh + 1 with qh = ph / SH. Likewise for columns.
+  const int qh = g.ph / SH, qw = g.pw / SW;
+  // patch row pr is go row i0 + qh - MR + pr, patch column lc is go column
+  // j0 - PADL + lc; by elements the columns from PADL + qw - MS are staged
+  P st;
+  st.locate(tid, i0 + qh - MR, j0 - PADL, PADL + qw - MS, g.H, g.W);
+
+  const int64_t wplane = (int64_t)g.Kp * g.Cp;
+  int64_t wrow[MF];
+#pragma unroll
+  for (int mf = 0; mf < MF; ++mf) {
+    const int row = k0 + mf * 16 + (lane & 15);
+    wrow[mf] = (int64_t)(row < g.Kp ? row : g.Kp - 1) * g.Cp + ((lane >> 4) << 3);
+  }
+  // Wt is the transposed pre-pass: the forward's tap (r, s) is its tap
+  // R*S - 1 - (r*S + s)
+  auto load_a = [&](s16x8 (&a)[MF], int r, int s, int c0) {
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf)
+      a[mf] = *(const s16x8*)(Wt + (R * S - 1 - (r * S + s)) * wplane +
+                              wrow[mf] + c0);
+  };
+
+  // B fragment nf: cell row frow, cell columns col0 .. col0 + 15, at the go
+  // pixel of m = MR, m' = MS of a class with both offsets qh, qw
+  int boff[NF];
+#pragma unroll
+  for (int nf = 0; nf < NF; ++nf) {
+    const int f = wid * NF + nf;
+    const int frow = f / FPR, col0 = (f % FPR) * 16;
+    boff[nf] = (frow * PWL + col0 + (lane & 15) + PADL + qw - MS) * PSTR +
+               ((lane >> 4) << 3);
+  }
+  // per class: its phase and the offset of its go pixels (uniform values)
+  int pa[SH], da[SH], pb_[SW], db[SW];
+#pragma unroll
+  for (int ra = 0; ra < SH; ++ra) {
+    pa[ra] = ((ra - g.ph) % SH + SH) % SH;
+    da[ra] = (pa[ra] + g.ph - ra) / SH - qh;
+  }
+#pragma unroll
+  for (int rb2 = 0; rb2 < SW; ++rb2) {
+    pb_[rb2] = ((rb2 - g.pw) % SW + SW) % SW;
+    db[rb2] = (pb_[rb2] + g.pw - rb2) / SW - qw;
+  }
+
+  f32x4 acc[SH * SW][MF][NF];
+#pragma unroll
+  for (int cl = 0; cl < SH * SW; ++cl)
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+      for (int nf = 0; nf < NF; ++nf)
+        acc[cl][mf][nf] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int chunks = g.Cp / CK;
+  s16x8 a_cur[MF], a_nxt[MF];
+  st.load(gn, HW, 0, g.C, tid);
+  load_a(a_cur, 0, 0, 0);
+  st.commit(lds, 0, g.C, tid);
+  __syncthreads();
+
+  for (int ch = 0; ch < chunks; ++ch) {
+    const bool more = ch + 1 < chunks;
+    if (more) st.load(gn, HW, (ch + 1) * CK, g.C, tid);
+    const short* pb = lds + (ch & 1) * PBUF;
+    // the taps class by class; every class has a first tap (SH <= R, SW <= S)
+#pragma unroll
+    for (int ra = 0; ra < SH; ++ra)
+#pragma unroll
+      for (int rb2 = 0; rb2 < SW; ++rb2) {
+        const int coff = (da[ra] * PWL + db[rb2]) * PSTR;
+#pragma unroll
+        for (int r = ra; r < R; r += SH)
+#pragma unroll
+          for (int s = rb2; s < S; s += SW) {
+            // the weights of the tap after this one, in walking order
+            if (s + SW < S)
+              load_a(a_nxt, r, s + SW, ch * CK);
+            else if (r + SH < R)
+              load_a(a_nxt, r + SH, rb2, ch * CK);
+            else if (rb2 + 1 < SW)
+              load_a(a_nxt, ra, rb2 + 1, ch * CK);
+            else if (ra + 1 < SH)
+              load_a(a_nxt, ra + 1, 0, ch * CK);
+            else if (more)
+              load_a(a_nxt, 0, 0, (ch + 1) * CK);
+            const int toff =
+                coff + ((MR - r / SH) * PWL + MS - s / SW) * PSTR;
+            s16x8 bfrag[NF];
+#pragma unroll
+            for (int nf = 0; nf < NF; ++nf)
+              bfrag[nf] = *(const s16x8*)(pb + boff[nf] + toff);
+#pragma unroll
+            for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+              for (int nf = 0; nf < NF; ++nf)
+                acc[ra * SW + rb2][mf][nf] =
+                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        a_cur[mf], bfrag[nf], acc[ra * SW + rb2][mf][nf], 0, 0,
+                        0);
+#pragma unroll
+            for (int mf = 0; mf < MF; ++mf) a_cur[mf] = a_nxt[mf];
+          }
+      }
+    if (more) st.commit(lds + ((ch & 1) ^ 1) * PBUF, (ch + 1) * CK, g.C, tid);
+    __syncthreads();
+  }
+
+  // epilogue: the classes interleaved in the [c][pixel] image of the EH x EW
+  // gx tile: cell (row, col) of phase (a, b) is pixel (row*SH + a, col*SW + b)
+  unsigned short* E = (unsigned short*)lds;
+#pragma unroll
+  for (int ra = 0; ra < SH; ++ra)
+#pragma unroll
+    for (int rb2 = 0; rb2 < SW; ++rb2)
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int k = mf * 16 + ((lane >> 4) << 2) + reg;
+#pragma unroll
+          for (int nf = 0; nf < NF; ++nf) {
+            const int f = wid * NF + nf;
+            const int pix = ((f / FPR) * SH + pa[ra]) * EW +
+                            ((f % FPR) * 16 + (lane & 15)) * SW + pb_[rb2];
+            E[k * ES + pix] = (unsigned short)(
+                pack_bf16(acc[ra * SW + rb2][mf][nf][reg], 0.f) & 0xffff);
+          }
+        }
+  __syncthreads();
+  strided_store<KB, EH, EW, ES>(E, gx, g, n, k0, i0 * SH, j0 * SW, tid);
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -1693,6 +2235,204 @@ torch::Tensor tap_fwd(torch::Tensor x, torch::Tensor w,
                      (const float*)part.data_ptr<float>(), bptr,
                      (unsigned short*)out.data_ptr(), sc, g.K, OHW, total);
   return out;
+}
+
+// ---- strided ----------------------------------------------------------------
+
+using BwdKern = void (*)(const unsigned short*, const unsigned short*,
+                         unsigned short*, TapGeom);
+
+// The instantiation of a strided problem: the only place that decides MF and
+// ALIGNED. Forward: the stride-1 chooser's MF. Data gradient: the same, but at
+// most 4 for 3x3, whose four classes hold 4 * MF * 2 accumulator fragments.
+struct StridedChoice {
+  Kern fwd;
+  BwdKern bwd;
+  int mf, th, tw, sh, sw;
+  std::string label;
+};
+
+template <int R, int S, int MF>
+static void strided_kernels(StridedChoice& c, bool aligned) {
+  c.fwd = aligned ? tap_strided_fwd_kernel<R, S, MF, true>
+                  : tap_strided_fwd_kernel<R, S, MF, false>;
+  c.bwd = aligned ? tap_strided_bwd_data_kernel<R, S, MF, true>
+                  : tap_strided_bwd_data_kernel<R, S, MF, false>;
+}
+
+template <int R, int S>
+static StridedChoice choose_strided_rs(int mf, bool transposed, bool aligned) {
+  using T = Strided<R, S>;
+  if (transposed && R == 3 && mf > 4) mf = 4;
+  StridedChoice c{nullptr, nullptr, mf, T::TH, T::TW, T::SH, T::SW,
+                  std::string(transposed ? "tap_strided_bwd<" : "tap_strided<") +
+                      std::to_string(R) + "x" + std::to_string(S) + "," +
+                      std::to_string(mf) + ">"};
+  if (mf == 2)
+    strided_kernels<R, S, 2>(c, aligned);
+  else if (mf == 4)
+    strided_kernels<R, S, 4>(c, aligned);
+  else if constexpr (R != 3)
+    strided_kernels<R, S, 7>(c, aligned);
+  else  // 3x3 forward only
+    c.fwd = aligned ? tap_strided_fwd_kernel<R, S, 7, true>
+                    : tap_strided_fwd_kernel<R, S, 7, false>;
+  return c;
+}
+
+// Kout: the output channels of the launch; Wst: the row length of the image
+// the launch stages (x, or go for the data gradient)
+static StridedChoice choose_strided(int Kout, int Wst, int R, int S,
+                                    bool transposed, bool base_aligned) {
+  const int mf = choose_mf(Kout);
+  const bool aligned = base_aligned && Wst % 8 == 0;
+  if (R == 1 && S == 7) return choose_strided_rs<1, 7>(mf, transposed, aligned);
+  if (R == 7 && S == 1) return choose_strided_rs<7, 1>(mf, transposed, aligned);
+  return choose_strided_rs<3, 3>(mf, transposed, aligned);
+}
+
+// (N, C, K, H, W): the forward convolution's, whichever leg is asked for
+static void check_strided(int64_t N, int64_t C, int64_t K, int64_t H, int64_t W,
+                          int64_t R, int64_t S, int64_t sh, int64_t sw,
+                          int64_t ph, int64_t pw, const char* who) {
+  TORCH_CHECK((R == 1 && S == 7) || (R == 7 && S == 1) || (R == 3 && S == 3),
+              who, ": kernel size must be 1x7, 7x1 or 3x3 (dilation 1, "
+              "groups 1), got ", R, "x", S);
+  TORCH_CHECK(sh == (R > 1 ? 2 : 1) && sw == (S > 1 ? 2 : 1),
+              who, ": stride must be (1, 2) for 1x7, (2, 1) for 7x1 and "
+              "(2, 2) for 3x3, got (", sh, ", ", sw, ") for ", R, "x", S);
+  TORCH_CHECK(N >= 1 && C >= 1 && K >= 1 && H >= 1 && W >= 1,
+              who, ": N, C, K, H, W must be positive");
+  TORCH_CHECK(ph >= 0 && ph <= R - 1 && pw >= 0 && pw <= S - 1,
+              who, ": padding must lie in [0, R-1] x [0, S-1], got (", ph,
+              ", ", pw, ") for ", R, "x", S);
+  TORCH_CHECK(H + 2 * ph >= R && W + 2 * pw >= S,
+              who, ": the padded input is smaller than the filter");
+  TORCH_CHECK(H * W < (1LL << 30) && C < (1LL << 24) && K < (1LL << 24),
+              who, ": problem too large");
+}
+
+// transposed: C the reduction dim and K the output channels of the launch (the
+// forward's K and C); H x W the forward's input in both cases
+std::string tap_strided_kernel_name(int64_t C, int64_t K, int64_t H, int64_t W,
+                                    int64_t R, int64_t S, int64_t sh,
+                                    int64_t sw, int64_t ph, int64_t pw,
+                                    bool transposed) {
+  check_strided(1, transposed ? K : C, transposed ? C : K, H, W, R, S, sh, sw,
+                ph, pw, "tap_strided_kernel_name");
+  const int64_t OW = (W + 2 * pw - S) / sw + 1;
+  return choose_strided((int)K, (int)(transposed ? OW : W), (int)R, (int)S,
+                        transposed, true).label;
+}
+
+static void check_strided_tensors(const torch::Tensor& a, const torch::Tensor& w,
+                                  const char* who) {
+  TORCH_CHECK(a.is_cuda() && w.is_cuda() && a.get_device() == w.get_device(),
+              who, ": the tensors must be on one GPU");
+  TORCH_CHECK(a.dim() == 4 && w.dim() == 4 && a.is_contiguous() &&
+                  w.is_contiguous(),
+              who, ": the tensors must be contiguous and 4-d");
+  TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
+                  w.scalar_type() == torch::kBFloat16,
+              who, ": bf16 only");
+}
+
+// The pre-pass and the main kernel of either leg. g.C / g.K: the reduction and
+// output channels of the launch; src: the staged image, dst: the result.
+static void launch_strided(const StridedChoice& ch, TapGeom g,
+                           const torch::Tensor& src, const torch::Tensor& w,
+                           const float* bias, torch::Tensor& dst,
+                           bool transposed, const char* who) {
+  const int64_t RS = w.size(2) * w.size(3);
+  g.Kp = (g.K + 15) / 16 * 16;
+  g.Cp = (g.C + CK - 1) / CK * CK;
+  g.k_tiles = (g.K + ch.mf * 16 - 1) / (ch.mf * 16);
+  g.vec_out = g.OW % 8 == 0 && ((uintptr_t)dst.data_ptr() & 15) == 0;
+  g.sc = 1;
+  auto Wt = torch::empty({RS, g.Kp, g.Cp}, src.options());
+  const int64_t fblocks = ((int64_t)g.Kp * g.Cp + 255) / 256;
+  const int64_t blocks =
+      (int64_t)g.k_tiles * g.row_blocks * g.col_blocks * g.N;
+  TORCH_CHECK(fblocks < (1LL << 31) && blocks < (1LL << 31), who,
+              ": grid too large");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(tap_filter_kernel, dim3((uint32_t)fblocks), dim3(256), 0,
+                     stream.stream(), (const unsigned short*)w.data_ptr(),
+                     (unsigned short*)Wt.data_ptr(), (int)w.size(1), g.K, g.C,
+                     g.Kp, g.Cp, (int)RS, transposed ? 1 : 0);
+  if (transposed)
+    hipLaunchKernelGGL(ch.bwd, dim3((uint32_t)blocks), dim3(256), 0,
+                       stream.stream(), (const unsigned short*)src.data_ptr(),
+                       (const unsigned short*)Wt.data_ptr(),
+                       (unsigned short*)dst.data_ptr(), g);
+  else
+    hipLaunchKernelGGL(ch.fwd, dim3((uint32_t)blocks), dim3(256), 0,
+                       stream.stream(), (const unsigned short*)src.data_ptr(),
+                       (const unsigned short*)Wt.data_ptr(), bias,
+                       (unsigned short*)dst.data_ptr(), g);
+}
+
+torch::Tensor tap_fwd_strided(torch::Tensor x, torch::Tensor w,
+                              c10::optional<torch::Tensor> bias, int64_t sh,
+                              int64_t sw, int64_t ph, int64_t pw) {
+  const char* who = "tap_fwd_strided";
+  check_strided_tensors(x, w, who);
+  const int64_t K = w.size(0), C = w.size(1), R = w.size(2), S = w.size(3);
+  check_strided(x.size(0), C, K, x.size(2), x.size(3), R, S, sh, sw, ph, pw,
+                who);
+  TORCH_CHECK(x.size(1) == C, who, ": channel mismatch: x has ", x.size(1),
+              ", the filter reduces over ", C);
+  const StridedChoice ch =
+      choose_strided((int)K, (int)x.size(3), (int)R, (int)S, false,
+                     ((uintptr_t)x.data_ptr() & 15) == 0);
+  TapGeom g;
+  g.N = (int)x.size(0); g.C = (int)C; g.K = (int)K;
+  g.H = (int)x.size(2); g.W = (int)x.size(3);
+  g.ph = (int)ph; g.pw = (int)pw;
+  g.OH = (g.H + 2 * g.ph - (int)R) / ch.sh + 1;
+  g.OW = (g.W + 2 * g.pw - (int)S) / ch.sw + 1;
+  g.row_blocks = (g.OH + ch.th - 1) / ch.th;
+  g.col_blocks = (g.OW + ch.tw - 1) / ch.tw;
+  const float* bptr = nullptr;
+  torch::Tensor b32;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->get_device() == x.get_device() &&
+                    bias->numel() == K,
+                who, ": bias must hold one value per output channel, on x's GPU");
+    b32 = bias->to(torch::kFloat).contiguous();
+    bptr = b32.data_ptr<float>();
+  }
+  auto out = torch::empty({g.N, g.K, g.OH, g.OW}, x.options());
+  launch_strided(ch, g, x, w, bptr, out, false, who);
+  return out;
+}
+
+torch::Tensor tap_bwd_data_strided(torch::Tensor go, torch::Tensor w, int64_t H,
+                                   int64_t W, int64_t sh, int64_t sw,
+                                   int64_t ph, int64_t pw) {
+  const char* who = "tap_bwd_data_strided";
+  check_strided_tensors(go, w, who);
+  const int64_t K = w.size(0), C = w.size(1), R = w.size(2), S = w.size(3);
+  check_strided(go.size(0), C, K, H, W, R, S, sh, sw, ph, pw, who);
+  const int64_t OH = (H + 2 * ph - R) / sh + 1, OW = (W + 2 * pw - S) / sw + 1;
+  TORCH_CHECK(go.size(1) == K && go.size(2) == OH && go.size(3) == OW, who,
+              ": go must be [N, ", K, ", ", OH, ", ", OW, "] for an input of ",
+              H, " x ", W);
+  const StridedChoice ch =
+      choose_strided((int)C, (int)OW, (int)R, (int)S, true,
+                     ((uintptr_t)go.data_ptr() & 15) == 0);
+  // the launch stages go and reduces over its channels; a block owns th x tw
+  // phase cells, that is (th*sh) x (tw*sw) pixels of gx
+  TapGeom g;
+  g.N = (int)go.size(0); g.C = (int)K; g.K = (int)C;
+  g.H = (int)OH; g.W = (int)OW;
+  g.ph = (int)ph; g.pw = (int)pw;
+  g.OH = (int)H; g.OW = (int)W;
+  g.row_blocks = ((g.OH + ch.sh - 1) / ch.sh + ch.th - 1) / ch.th;
+  g.col_blocks = ((g.OW + ch.sw - 1) / ch.sw + ch.tw - 1) / ch.tw;
+  auto gx = torch::empty({g.N, g.K, g.OH, g.OW}, go.options());
+  launch_strided(ch, g, go, w, nullptr, gx, true, who);
+  return gx;
 }
 
 // ---- weight gradient --------------------------------------------------------
@@ -2068,6 +2808,26 @@ void register_conv_tap(pybind11::module_& m) {
         "(label, slices) of the launch of tap_fwd(split=-1) for (N, C, K, H, "
         "W, R, S, ph, pw) on a device of `cus` compute units; slices == 1: "
         "tap_kernel_name's kernel; no tensor, no HIP call");
+  m.def("tap_fwd_strided", &conv_tap::tap_fwd_strided, pybind11::arg("x"),
+        pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("sh"),
+        pybind11::arg("sw"), pybind11::arg("ph"), pybind11::arg("pw"),
+        "tap-shift direct strided conv: 1x7 at stride (1, 2), 7x1 at (2, 1), "
+        "3x3 at (2, 2) (bf16 NCHW), the input patch staged in phase planes");
+  m.def("tap_bwd_data_strided", &conv_tap::tap_bwd_data_strided,
+        pybind11::arg("go"), pybind11::arg("w"), pybind11::arg("H"),
+        pybind11::arg("W"), pybind11::arg("sh"), pybind11::arg("sw"),
+        pybind11::arg("ph"), pybind11::arg("pw"),
+        "data gradient [N, C, H, W] of the convolution tap_fwd_strided runs, "
+        "by phase decomposition of go (no zero-stuffing); w is the forward "
+        "weight");
+  m.def("tap_strided_kernel_name", &conv_tap::tap_strided_kernel_name,
+        pybind11::arg("C"), pybind11::arg("K"), pybind11::arg("H"),
+        pybind11::arg("W"), pybind11::arg("R"), pybind11::arg("S"),
+        pybind11::arg("sh"), pybind11::arg("sw"), pybind11::arg("ph"),
+        pybind11::arg("pw"), pybind11::arg("transposed") = false,
+        "label of the kernel tap_fwd_strided or (transposed: C the reduction "
+        "dim, K the output channels of the launch) tap_bwd_data_strided "
+        "launches; H x W is the forward's input; no tensor, no HIP call");
   m.def("tap_bwd_weight", &conv_tap::tap_bwd_weight, pybind11::arg("go"),
         pybind11::arg("x"), pybind11::arg("R"), pybind11::arg("S"),
         pybind11::arg("ph"), pybind11::arg("pw"),

@@ -55,7 +55,18 @@ Kernel families (csrc/):
   of blocks that leave fp32 partial sums in a workspace, and
   tap_split_reduce_kernel adds them in slice order, with the bias, and
   rounds once; elsewhere it is the unsplit kernel (PERF_NOTES, "Tap-shift
-  conv, split channels").
+  conv, split channels"). MPI4DL_TAPCONV_STRIDED=1, also on top of the
+  first switch, routes the strided problems of the same three filter
+  shapes (1x7 at stride (1, 2), 7x1 at (2, 1), 3x3 at (2, 2): AmoebaNet's
+  reduction cells and the head of every ResNet stage) to
+  ge.tap_fwd_strided and ge.tap_bwd_data_strided:
+  tap_strided_fwd_kernel stages the input patch in phase planes (column
+  lc in plane lc % sw), so a tap of 16 output columns is again one
+  contiguous run of LDS pixels, and tap_strided_bwd_data_kernel computes
+  the data gradient by phase decomposition, every tap class of the filter
+  against one staged patch of go: no zero-stuffed copy and none of its
+  multiply-adds by zero. The weight-grad stays on conv_bwd_weight
+  (PERF_NOTES, "Tap-shift conv, strided").
 
 Per-shape, per-LEG policy (all crossovers measured on MI355X —
 profiles/PERF_NOTES.md): stride-2 1x1s, K<=64 1x1s, stems, wide
@@ -68,15 +79,15 @@ F.conv2d/MIOpen. MPI4DL_NATIVE_CONV=0 disables all native paths,
 
 The per-leg policy is written once, in ``conv_plan``: a pure function
 of the problem's integers and the MPI4DL_PW_BLASLT,
-MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1, MPI4DL_TAPCONV_WGRAD=1|ring|px
-and MPI4DL_TAPCONV_SPLIT=auto switches. ``ConvFn`` executes the plan and
-decides nothing itself; which kernel a native route then launches is the
+MPI4DL_WINOGRAD=fused, MPI4DL_TAPCONV=1, MPI4DL_TAPCONV_WGRAD=1|ring|px,
+MPI4DL_TAPCONV_SPLIT=auto and MPI4DL_TAPCONV_STRIDED=1 switches.
+``ConvFn`` executes the plan and decides nothing itself; which kernel a native route then launches is the
 extension's choice
 (``conv_fwd_kernel_name``, ``pw_kernel_name``, ``pw_bwdw_kernel_name``,
 ``wino_kernel_name``, ``tap_kernel_name``, ``tap_split_kernel_name``,
 ``tap_bwdw_kernel_name``,
-``tap_bwdw_ring_kernel_name``, ``tap_bwdw_px_kernel_name`` answer it for a
-plan's problems).
+``tap_bwdw_ring_kernel_name``, ``tap_bwdw_px_kernel_name``,
+``tap_strided_kernel_name`` answer it for a plan's problems).
 """
 
 from __future__ import annotations
@@ -144,6 +155,21 @@ def _tap_split_on():
     return os.environ.get("MPI4DL_TAPCONV_SPLIT", "0") == "auto"
 
 
+def _tap_strided_on():
+    return os.environ.get("MPI4DL_TAPCONV_STRIDED", "0") == "1"
+
+
+def _tap_strided_ok(H, W, R, S, sh, sw, ph, pw):
+    """What conv_tap.hip's strided kernels serve: 1x7 at stride (1, 2), 7x1
+    at (2, 1) or 3x3 at (2, 2), pads in [0, R-1] x [0, S-1], at least one
+    output pixel (dilation 1 and groups 1 are the caller's)."""
+    return (
+        (R, S, sh, sw) in ((1, 7, 1, 2), (7, 1, 2, 1), (3, 3, 2, 2))
+        and 0 <= ph <= R - 1 and 0 <= pw <= S - 1
+        and H + 2 * ph >= R and W + 2 * pw >= S
+    )
+
+
 def _tap_ok(H, W, R, S, sh, sw, ph, pw):
     """What conv_tap.hip serves: 1x7, 7x1 or 3x3, stride 1, pads in
     [0, R-1] x [0, S-1], at least one output pixel (dilation 1 and groups
@@ -190,6 +216,13 @@ class Leg(NamedTuple):
                              tap_bwdw_ring_kernel_name's, the same nine
       tap_bwd_weight_px      ge.tap_bwd_weight_px; problem =
                              tap_bwdw_px_kernel_name's, the same nine
+      tap_fwd_strided        ge.tap_fwd_strided; problem =
+                             tap_strided_kernel_name's
+                             (C, K, H, W, R, S, sh, sw, ph, pw)
+      tap_bwd_data_strided   ge.tap_bwd_data_strided; problem = (K, C, OH, OW,
+                             H, W, R, S, sh, sw, ph, pw): K the reduction dim
+                             and C the output channels of the launch, OH x OW
+                             the extents of go, the rest the forward's
     """
 
     route: str
@@ -203,7 +236,8 @@ class ConvPlan(NamedTuple):
 
 
 def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
-              winograd=None, tap=None, tap_wgrad=None, tap_split=None):
+              winograd=None, tap=None, tap_wgrad=None, tap_split=None,
+              tap_strided=None):
     """The route of each leg of the convolution x[N,C,H,W] * w[K,C,R,S]
     and the problem that route hands to its binding. ``blaslt`` defaults
     to the MPI4DL_PW_BLASLT switch, ``winograd`` to
@@ -211,7 +245,8 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
     ``tap_wgrad`` (looked at only where ``tap`` routes the problem; True,
     False, "ring" or "px") to MPI4DL_TAPCONV_WGRAD == "1", "ring" or "px"
     and ``tap_split`` (looked at only where ``tap`` routes the problem) to
-    MPI4DL_TAPCONV_SPLIT == "auto"; nothing else is read."""
+    MPI4DL_TAPCONV_SPLIT == "auto" and ``tap_strided`` (looked at only where
+    ``tap`` is on) to MPI4DL_TAPCONV_STRIDED == "1"; nothing else is read."""
     if blaslt is None:
         blaslt = _blaslt_on()
     if winograd is None:
@@ -286,6 +321,19 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
              else Leg("tap_bwd_weight", tapw) if tap_wgrad
              else Leg("conv_bwd_weight", fwd)),
         )
+    if tap and _tap_strided_ok(H, W, R, S, sh, sw, ph, pw):
+        if tap_strided is None:
+            tap_strided = _tap_strided_on()
+        if tap_strided:
+            # opt-in strided tap-shift kernels: the forward on a phase-split
+            # patch, the data-grad by phase decomposition of go; the
+            # weight-grad keeps its kernel, which is strided already
+            return ConvPlan(
+                Leg("tap_fwd_strided", fwd),
+                Leg("tap_bwd_data_strided",
+                    (K, C, OH, OW, H, W, R, S, sh, sw, ph, pw)),
+                Leg("conv_bwd_weight", fwd),
+            )
     if (sh, sw) == (1, 1):
         # stride-1 data-grad = the forward kernel on C<->K transposed,
         # 180-rotated weights
@@ -305,9 +353,9 @@ def conv_plan(N, C, K, H, W, R, S, sh, sw, ph, pw, blaslt=None,
 class ConvFn(torch.autograd.Function):
     """Executes ``conv_plan``. The plan is made once, in forward, and
     kept on ctx: backward reads none of MPI4DL_PW_BLASLT,
-    MPI4DL_WINOGRAD, MPI4DL_TAPCONV, MPI4DL_TAPCONV_WGRAD and
-    MPI4DL_TAPCONV_SPLIT again, so a change of a variable between a forward
-    and its backward is ignored.
+    MPI4DL_WINOGRAD, MPI4DL_TAPCONV, MPI4DL_TAPCONV_WGRAD,
+    MPI4DL_TAPCONV_SPLIT and MPI4DL_TAPCONV_STRIDED again, so a change of
+    a variable between a forward and its backward is ignored.
 
     Weight gradient: the routes that run our own kernels (pw_bwdw,
     pw_bwdw_sub, conv_bwd_weight, tap_bwd_weight, tap_bwd_weight_ring,
@@ -336,6 +384,8 @@ class ConvFn(torch.autograd.Function):
             y = ge.tap_fwd(xb, wb, bias, ph, pw)
         elif plan.y.route == "tap_fwd_split":
             y = ge.tap_fwd(xb, wb, bias, ph, pw, split=-1)
+        elif plan.y.route == "tap_fwd_strided":
+            y = ge.tap_fwd_strided(xb, wb, bias, sh, sw, ph, pw)
         else:
             y = ge.conv_fwd(xb, wb, bias, sh, sw, ph, pw)
         ctx.save_for_backward(xb, wb)
@@ -407,6 +457,9 @@ class ConvFn(torch.autograd.Function):
         elif gx_route == "tap_fwd_split":
             gx = ge.tap_fwd(go, wb, None, R - 1 - ph, S - 1 - pw, True,
                             split=-1)
+        elif gx_route == "tap_bwd_data_strided":
+            # the filter pre-pass reads wb transposed and rotated itself
+            gx = ge.tap_bwd_data_strided(go, wb, H, W, sh, sw, ph, pw)
         else:
             # conv_fwd on go, or on go zero-stuffed to the plan's extents
             _, _, hs, ws, _, _, _, _, tph, tpw = ctx.plan.gx.problem
@@ -483,7 +536,8 @@ def _wino_dispatchable(x, conv: nn.Conv2d) -> bool:
 
 def _tap_dispatchable(x, conv: nn.Conv2d) -> bool:
     """MPI4DL_TAPCONV=1: a supported 1x7, 7x1 or 3x3 on a CUDA tensor,
-    under the bf16/autocast condition of ``_dispatchable``."""
+    under the bf16/autocast condition of ``_dispatchable``; with
+    MPI4DL_TAPCONV_STRIDED=1 as well, also their strided problems."""
     if not _tap_on():
         return False
     if not (x.is_cuda and not x.is_meta) or x.dim() != 4:
@@ -494,8 +548,9 @@ def _tap_dispatchable(x, conv: nn.Conv2d) -> bool:
         return False
     if isinstance(conv.padding, str) or conv.padding_mode != "zeros":
         return False
-    return _tap_ok(x.shape[-2], x.shape[-1], *_pair(conv.kernel_size),
-                   *_pair(conv.stride), *_pair(conv.padding))
+    geom = (x.shape[-2], x.shape[-1], *_pair(conv.kernel_size),
+            *_pair(conv.stride), *_pair(conv.padding))
+    return _tap_ok(*geom) or (_tap_strided_on() and _tap_strided_ok(*geom))
 
 
 class NativeConv2d(nn.Conv2d):
